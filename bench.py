@@ -285,6 +285,60 @@ def pmc_profile(key, source_hash):
     return entry
 
 
+DUMP_BUDGET = 48 << 20   # bytes of arrays --dump-outputs writes (the whole dump stays under 64 MB)
+
+
+def dump_plan(chains_total, dim, n_iters, n_stats, budget=DUMP_BUDGET):
+    """What --dump-outputs keeps of the last step: (sorted global chain indices, iterations) -- a fixed, seeded sample of
+    the job's chains (the same for every build and run with the same arguments) and the step's last `iterations`
+    iterations, so that draws, statistics and final positions of the sample fit `budget` bytes in float64."""
+    per_iter = 8 * (dim + n_stats)
+    n_it = max(1, min(n_iters, budget // (64 * per_iter)))
+    n_chains = max(1, min(chains_total, 1024, budget // (n_it * per_iter + 8 * dim)))
+    idx = np.random.default_rng(SEED).choice(chains_total, n_chains, replace=False)
+    return np.sort(idx), n_it
+
+
+def dump_outputs(out_dir, engs, parts, step, idx, first, n_it, trace_begin, gather=None):
+    """Write what the timed path computed in its last step for the global chains `idx` (dump_plan()), as `sample()` hands
+    it to a caller: `trace` [chains, n_it, dim] (when the job keeps draws), one array [chains, n_it] per statistic under the names
+    of step.stats_dtypes, the final `position` [chains, dim] and `chain_index` (global chain index of every row) -- all
+    float64, one DIR/<name>.npy each. Iterations [first, first + n_it). `gather` (several ranks): exchanges every rank's
+    rows; rank 0 writes."""
+    rows = {}
+    for eng, part in zip(engs, parts):
+        mine = idx[(idx >= part["lo"]) & (idx < part["hi"])]
+        if not len(mine):
+            continue
+        local = mine - part["lo"]
+        got = {"chain_index": mine.astype(np.float64), "position": eng.get_position()[local]}
+        stats = step._stats_from_engine(eng, first, n_it)
+        for name in step.stats_dtypes[0]:
+            got[name] = np.asarray(stats[name])[local].astype(np.float64)
+        if trace_begin is not None and first >= trace_begin:
+            import torch
+
+            from littlemcmc_amd import diagnostics as dg
+
+            view = dg.trace_tensor(eng)
+            sel = torch.as_tensor(local, device=view.device)
+            got["trace"] = view[sel, first - trace_begin:first - trace_begin + n_it].double().cpu().numpy()
+        for name, arr in got.items():
+            rows.setdefault(name, []).append(arr)
+    if gather is not None:
+        rows = gather(rows)
+        if rows is None:
+            return None
+    order = np.argsort(np.concatenate(rows["chain_index"]), kind="stable")
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, parts_ in rows.items():
+        arr = np.ascontiguousarray(np.concatenate(parts_)[order], dtype=np.float64)
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+        total += arr.nbytes
+    return total
+
+
 def self_launch(n):
     """``python bench.py --gpus N`` without a launcher: re-run this very command line as N ranks (one per GPU) under
     ``torch.distributed.run`` on 127.0.0.1 with a free port; rank 0 prints the one JSON line, which passes through."""
@@ -335,6 +389,10 @@ def main():
     ap.add_argument("--no-philox-line", action="store_true", help="skip the separately labelled counter-based-RNG line of the north_star shape")
     ap.add_argument("--no-tail", action="store_true", help="skip the lone-chain latency measurement of the tail block (profiling "
                                                            "runs: keeps every run_kernel dispatch the same size)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the primary workload computed in its LAST step -- draws, statistics "
+                         "and final positions of a fixed, seeded sample of its chains, float64 -- as DIR/<name>.npy (< 64 MB in "
+                         "all): two builds run with the same arguments can be compared output for output")
     ap.add_argument("--detail-out", default=None, help="where the verbose result object goes (default: bench_detail.json next to "
                                                        "bench.py); stdout carries one compact line of at most %d bytes" % LINE_LIMIT)
     ap.add_argument("--no-rccl-check", action="store_true", help="N = 1: do not bring up the one-rank RCCL group")
@@ -447,6 +505,8 @@ def main():
     from littlemcmc_amd.distributed import chain_block
 
     K, W, ips = args.steps, args.warmup, args.iters_per_step
+    if K < 1 or W < 0 or ips < 1:
+        raise SystemExit("--steps and --iters-per-step must be >= 1 and --warmup >= 0")
     n_total = K * ips
     n_tune = n_total // 2
     n_units = args.gpus if inproc else world          # GPUs (chain blocks) of the job
@@ -500,10 +560,22 @@ def main():
         dist.all_gather(out, t)
         return [[float(v) for v in o] for o in out]
 
+    def gather_rows(rows):
+        """--dump-outputs on several ranks: every rank's {name: [arrays]} -> the union on rank 0 (None elsewhere)"""
+        got = [None] * world
+        dist.all_gather_object(got, rows)
+        if rank != 0:
+            return None
+        merged = {}
+        for r_ in got:
+            for name, arrs in r_.items():
+                merged.setdefault(name, []).extend(arrs)
+        return merged
+
     RNG_LABEL = {"numpy": "MT19937 (numpy legacy stream, same-seed parity mode)",
                  "philox": "Philox4x32-10 momentum stream (throughput mode: NOT the reference's draws), tree uniforms MT19937"}
 
-    def run_job(target_name, dim, with_ess, rng="numpy", job_chains=None, max_treedepth=None, K=K, ips=ips, tag=""):
+    def run_job(target_name, dim, with_ess, rng="numpy", job_chains=None, max_treedepth=None, K=K, ips=ips, tag="", dump_dir=None):
         """The timed job on this process's chain block(s) -> dict of measurements (wall / leapfrogs reduced over ranks).
         Defaults = the primary workload of the command line; the BASELINE configurations that ride along as `secondary`
         lines name their own chains / tree depth / launch split."""
@@ -707,6 +779,10 @@ def main():
                    "lag_passes": int(diag.get("lag_passes", 0)),
                    "draw_seconds": draw_s, "chains_total": int(diag["n_chains"] / 2), "draws": n_total - trace_begin,
                    "diagnostics_seconds": diag_s, "diagnostics_process_warmup_seconds": diag_first_s, "definition": diag.get("definition", "")}
+        if dump_dir is not None:   # after everything timed: the last step's outputs of a fixed sample of chains
+            idx, n_it = dump_plan(chains_total, dim, ips, len(step.stats_dtypes[0]))
+            dump_outputs(dump_dir, engs, parts, step, idx, n_total - n_it, n_it, trace_begin if keep_trace else None,
+                         gather=gather_rows if world > 1 else None)
         for e_ in engs:
             e_.close()
 
@@ -794,7 +870,7 @@ def main():
             r["pmc_source"] = prof.get("source")
         return r
 
-    primary = run_job(args.target, args.dim, with_ess=True, rng=args.rng)
+    primary = run_job(args.target, args.dim, with_ess=True, rng=args.rng, dump_dir=args.dump_outputs)
     # The other BASELINE.json configurations ride along as `secondary` lines, each timed exactly like the primary (barrier,
     # HIP events on the launch streams, max over ranks) with its own roofline and tail block: north_star's named shape in
     # both RNG modes, C2, C4, and C5 both as K launches and as ONE launch (what sample() does; C5 is tail-bound, so the

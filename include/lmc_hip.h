@@ -137,7 +137,7 @@ typedef struct lmc_engine lmc_engine;
  * library -- hidden inputs to an ABI that takes everything else through lmc_config; the Python host still honours the
  * variables of the same names (littlemcmc_amd/engine.py: tuning_from_env), but it is the host that reads them. */
 typedef struct lmc_tuning {
-    int32_t sub_blocks;           /* sub-block streams lmc_engine_run() deals the chains to: 1 .. 4 (LMC_SUB_BLOCKS) */
+    int32_t sub_blocks;           /* sub-block streams lmc_engine_run() deals the chains to: 1 .. 4 (LMC_SUB_BLOCKS); -n: at most n */
     int32_t force_general;        /* 1: every shape the general kernels support runs in them (LMC_FORCE_WIDE) */
     int32_t general_team;         /* 16: the general kernels' 16-wavefront team at every shape (LMC_WIDE_TEAM) */
     int32_t run_ns, run_w;        /* shape of the fused sampling kernel, 64 * run_ns * run_w = padded dim (LMC_RUN_SHAPE="ns,w") */

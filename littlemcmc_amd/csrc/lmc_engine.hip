@@ -869,6 +869,15 @@ int lmc_engine_create(const lmc_config* cfg, lmc_engine** out) {
     if (e->n_sub > 2 && cfg->potential >= LMC_POT_FULL) e->n_sub = 2;
     if (cfg->tuning.sub_blocks >= 1 && cfg->tuning.sub_blocks <= lmc_engine::kMaxSub && cfg->tuning.sub_blocks <= cfg->chains)
         e->n_sub = cfg->tuning.sub_blocks;
+    // a negative value caps the engine's own choice instead: the host passes minus the hardware queues the runtime has per
+    // priority (GPU_MAX_HW_QUEUES). Two sub-block streams on one queue run one after the other, so with fewer queues than
+    // sub-blocks the later sub-blocks start only when the earlier ones' launch is over -- and an interrupt before that found
+    // chains that had not begun and returned no draw at all (tests/test_gpu_scale.py, tests/test_gpu_round5.py).
+    if (cfg->tuning.sub_blocks <= -1 && e->n_sub > -cfg->tuning.sub_blocks) e->n_sub = -cfg->tuning.sub_blocks;
+    // the dense-mass kernels take one stream under such a cap: the pool is shared with every other stream of the process and
+    // a new stream gets its least used queue, so two sub-blocks may still share one -- and a shared-matrix workgroup holds a
+    // whole CU, so the second dispatch waited out the first's launch (tests/test_gpu_dense.py, Ctrl-C found no draw)
+    if (cfg->tuning.sub_blocks <= -1 && cfg->potential >= LMC_POT_FULL) e->n_sub = 1;
     if (e->n_sub > 1) {
         for (int b = 0; b < e->n_sub; ++b) {
             se = hipStreamCreateWithFlags(&e->sub_stream[b], hipStreamNonBlocking);

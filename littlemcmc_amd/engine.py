@@ -193,6 +193,20 @@ def tuning_from_env(environ=None):
     return out
 
 
+def hw_queue_cap(environ=None):
+    """Hardware queues the HIP runtime gives the streams of one priority (GPU_MAX_HW_QUEUES; None: the runtime's default of
+    four, which the engine's sub-blocks already fit). An engine takes at most this many sub-block streams when the caller
+    leaves the number open: sub-block streams that share a queue run one after the other."""
+    import os
+
+    environ = os.environ if environ is None else environ
+    try:
+        n = int(environ.get("GPU_MAX_HW_QUEUES", ""))
+    except ValueError:
+        return None
+    return n if 1 <= n < 4 else None
+
+
 class Engine:
     def __init__(self, target, chains, kind="nuts", potential="diag_adapt", device=0, lib_path=None,
                  target_accept=0.8, Emax=1000.0, adapt_step_size=True, step_scale=0.25, gamma=0.05, k=0.75,
@@ -238,6 +252,8 @@ class Engine:
                         1: _abi.LDS_PLAN_DEEP, "deep": _abi.LDS_PLAN_DEEP}[lds_plan]
         for field, value in (tuning_from_env() if tuning is None else dict(tuning)).items():   # struct lmc_tuning: test / A-B knobs
             setattr(cfg.tuning, field, int(value))
+        if cfg.tuning.sub_blocks == 0 and hw_queue_cap() is not None:   # left open: at most one sub-block per hardware queue
+            cfg.tuning.sub_blocks = -hw_queue_cap()
         cfg.rng_mode = {"numpy": _abi.RNG_NUMPY, "philox": _abi.RNG_PHILOX}[rng]   # include/lmc_hip.h: LMC_RNG_*
         # QuadPotentialDiagAdapt(dtype=...) (quadpotential.py:159,175-184); float64 runs in the general kernels
         # QuadPotentialFullAdapt(dtype=...) (quadpotential.py:484,497-509) likewise: float64 covariance, factor and momentum

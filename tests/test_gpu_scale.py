@@ -7,6 +7,7 @@ import pytest
 import littlemcmc_amd as lmc
 from littlemcmc_amd import _abi
 from littlemcmc_amd import targets as T
+from littlemcmc_amd.engine import hw_queue_cap
 
 pytestmark = pytest.mark.gpu
 
@@ -72,8 +73,8 @@ def test_chain_block_prefix_stability_and_launch_slicing():
 
 def test_sub_block_streams_do_not_change_a_bit(monkeypatch):
     """lmc_engine_run launches the chains as four contiguous sub-blocks on four internal streams (two until round 5; the
-    tail of one sub-block's launch is covered by the others' next launches). Same job, launched as ONE block and as TWO:
-    identical draws, statistics and adaptation
+    tail of one sub-block's launch is covered by the others' next launches; at most one per hardware queue of the runtime,
+    engine.hw_queue_cap). Same job, launched as ONE block, as TWO and as FOUR: identical draws, statistics and adaptation
     state -- with reads, position pushes and other entry points interleaved between the launches."""
     d, tune, draws, chains = 48, 70, 30, 513
     tgt = T.AR1(d, 0.9)
@@ -86,7 +87,7 @@ def test_sub_block_streams_do_not_change_a_bit(monkeypatch):
             monkeypatch.setenv("LMC_SUB_BLOCKS", str(sub_blocks))
         start, step = lmc.init_nuts(tgt, d, random_seed=seeds)
         eng = step._make_engine(chains)
-        assert len(eng.run_streams()) == (4 if sub_blocks is None else sub_blocks)
+        assert len(eng.run_streams()) == ((hw_queue_cap() or 4) if sub_blocks is None else sub_blocks)
         eng.seed(seeds); eng.set_position(start); eng.reset_tuning()
         eng.reserve(tune + draws, keep_trace=True, trace_begin=0)
         eng.run(tune, 0, 13)
@@ -100,7 +101,7 @@ def test_sub_block_streams_do_not_change_a_bit(monkeypatch):
         return out
 
     a = job(None)
-    for b in (job(1), job(2)):
+    for b in (job(1), job(2), job(4)):
         for x, y in zip(a, b):
             if x.ndim == 2 and x.shape[1] == _abi.NUM_COUNTERS:     # the residency clock (CT_WAVE_TICKS) is a timing, not a result
                 x, y = x[:, :_abi.CT_WAVE_TICKS], y[:, :_abi.CT_WAVE_TICKS]
@@ -110,7 +111,8 @@ def test_sub_block_streams_do_not_change_a_bit(monkeypatch):
 
 def test_sub_block_streams_dense_mass(monkeypatch):
     """The dense-mass kernels go out as sub-blocks too (with FullAdapt: run kernel + covariance refresh per tuning
-    iteration, chained per sub-block): same draws and statistics as launched in one block."""
+    iteration, chained per sub-block; one block when the runtime has fewer hardware queues than four): same draws and
+    statistics as launched in one block and in two."""
     d, tune, draws, chains = 10, 40, 12, 300
     tgt = T.AR1(d, 0.9)
 
@@ -122,10 +124,11 @@ def test_sub_block_streams_dense_mass(monkeypatch):
         return lmc.sample(tgt, d, draws=draws, tune=tune, chains=chains, init="jitter+adapt_full", random_seed=3,
                           discard_tuned_samples=False)
 
-    (ta, sa), (tb, sb) = job(None), job(1)
-    np.testing.assert_array_equal(ta, tb)
-    for k in sa:
-        np.testing.assert_array_equal(sa[k], sb[k])
+    (ta, sa) = job(None)
+    for tb, sb in (job(1), job(2)):
+        np.testing.assert_array_equal(ta, tb)
+        for k in sa:
+            np.testing.assert_array_equal(sa[k], sb[k])
 
 
 def test_checkpoint_resume_is_bit_identical():

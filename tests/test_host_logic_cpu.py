@@ -422,3 +422,24 @@ def test_pinned_arrays_own_whole_pages_and_register_where_they_are_told():
     gc.collect()
     assert len(lib.unreg) == 3
     assert engine.pinned_empty((0, 4), np.float64, lib=lib).shape == (0, 4) and len(lib.reg) == 3   # nothing to pin
+
+
+def test_bench_dump_plan_is_fixed_and_bounded():
+    """bench.py --dump-outputs: the sample of chains and iterations depends on the arguments only (two builds compare the
+    same rows), holds distinct chains of the job in order, and keeps the dump under 64 MB whatever the shape."""
+    import importlib
+
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+    n_stats = 11   # NUTS: the eleven statistics sample() returns
+    for chains, dim, ips in ((65536, 128, 100), (4096, 64, 100), (16384, 256, 2000), (8, 3, 7), (1, 100000, 50)):
+        idx, n_it = bench.dump_plan(chains, dim, ips, n_stats)
+        again, n_it2 = bench.dump_plan(chains, dim, ips, n_stats)
+        np.testing.assert_array_equal(idx, again)
+        assert n_it == n_it2 and 1 <= n_it <= ips
+        assert len(idx) >= 1 and len(np.unique(idx)) == len(idx) and np.all(np.diff(idx) > 0)
+        assert idx.min() >= 0 and idx.max() < chains
+        total = len(idx) * (n_it * 8 * (dim + n_stats) + 8 * dim + 8)   # trace + statistics + position + chain_index
+        assert total < 64e6, (chains, dim, ips, total)
+    idx, n_it = bench.dump_plan(65536, 128, 100, n_stats)
+    assert n_it == 100 and len(idx) >= 256    # the headline's last step whole, for a few hundred chains
