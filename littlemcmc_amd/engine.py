@@ -376,6 +376,7 @@ class Engine:
         self.capacity = int(capacity)
         self.keep_trace = bool(keep_trace) and tb < capacity
         self.trace_begin = max(tb, 0)
+        self._trace_out = None           # (reserve detached it: the engine writes its own trace, or none)
 
     def attach_trace(self, out, trace_begin):
         """Where the draws of iterations >= trace_begin go, after reserve(keep_trace=False): ``out`` = a device-accessible
@@ -788,6 +789,7 @@ class EngineGroup:
     def attach_trace(self, out, trace_begin):
         for e, (lo, hi) in zip(self.engines, self.blocks):
             e.attach_trace(None if out is None else out[lo:hi], trace_begin)
+        self.keep_trace, self.trace_begin = self.engines[0].keep_trace, self.engines[0].trace_begin
 
     def copy_wait(self):
         self._each("copy_wait")

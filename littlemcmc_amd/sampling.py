@@ -263,14 +263,20 @@ def _run_job(eng, tune, n_total, per_launch, progressbar, callback=None, on_enqu
             eng.synchronize()
         return n_total, False
     except KeyboardInterrupt:
-        if eng.target.family != _abi.TARGET_EXTERNAL:
-            eng.request_stop(True)
-        eng.synchronize()
-        n_done = min(eng.completed_iterations(), n_total)
-        if eng.target.family != _abi.TARGET_EXTERNAL:
-            eng.request_stop(False)     # re-armed for whoever keeps the engine (return_engine=True)
-        _log.warning("Sampling interrupted after %d of %d iterations; returning the draws so far." % (n_done, n_total))
-        return n_done, True
+        return _interrupted(eng, n_total, stop_device=eng.target.family != _abi.TARGET_EXTERNAL)
+
+
+def _interrupted(eng, n_total, stop_device):
+    """How a job loop ends on Ctrl-C: (``stop_device``) every chain leaves its launch at its next iteration boundary and
+    the launches still queued do nothing; wait for the device; returns (iterations completed by EVERY chain, True)."""
+    if stop_device:
+        eng.request_stop(True)
+    eng.synchronize()
+    n_done = min(eng.completed_iterations(), n_total)
+    if stop_device:
+        eng.request_stop(False)     # re-armed for whoever keeps the engine (return_engine=True)
+    _log.warning("Sampling interrupted after %d of %d iterations; returning the draws so far." % (n_done, n_total))
+    return n_done, True
 
 
 def _run_job_host_step_rand(eng, step, tune, n_total, progressbar, callback=None):
@@ -295,10 +301,7 @@ def _run_job_host_step_rand(eng, step, tune, n_total, progressbar, callback=None
         eng.synchronize()
         return n_total, False
     except KeyboardInterrupt:
-        eng.synchronize()
-        n_done = min(eng.completed_iterations(), n_total)
-        _log.warning("Sampling interrupted after %d of %d iterations; returning the draws so far." % (n_done, n_total))
-        return n_done, True
+        return _interrupted(eng, n_total, stop_device=False)   # (at most one iteration is in flight)
     finally:
         # whoever keeps the engine (return_engine=True) gets it back without the per-chain override, interrupted or not;
         # a failure in here must not mask the error that brought us here (a HIP error usually makes synchronize() fail too)
@@ -345,6 +348,123 @@ def _resolve_devices(devices, device, cores, chains, probe):
             devices = list(range(max(1, min(n_vis, chains // slots))))
     return devices[:max(1, min(len(devices), chains))]
 
+
+def _start_points(start, chains, model_ndim):
+    """[chains, model_ndim] start positions from one point for every chain or one per chain (sampling.py:161-164)."""
+    if isinstance(start, (list, tuple)):
+        if len(start) != chains:
+            raise ValueError("start list must have one entry per chain")
+        start = np.stack([np.asarray(x, dtype="d") for x in start])
+    start = np.asarray(start, dtype="d")
+    if start.ndim == 1:   # same start for every chain (sampling.py:163-164)
+        return np.broadcast_to(start, (chains, model_ndim))
+    if start.shape != (chains, model_ndim):
+        raise ValueError("start must have shape (model_ndim,) or (chains, model_ndim)")
+    return start
+
+
+def _make_engines(step, chains, devs):
+    """One Engine on one device; on several, an EngineGroup of one engine per contiguous chain block
+    (distributed.chain_block). If an engine cannot be made, the ones made before it are closed."""
+    if len(devs) == 1:
+        return step._make_engine(chains, device=devs[0])
+    from .distributed import chain_block
+    from .engine import EngineGroup
+
+    blocks = [chain_block(chains, k, len(devs)) for k in range(len(devs))]
+    made = []
+    try:
+        for dv, (b_lo, b_hi) in zip(devs, blocks):
+            made.append(step._make_engine(b_hi - b_lo, device=dv))
+    except BaseException:
+        for e_ in made:
+            e_.close()
+        raise
+    _log.info("Sampling %d chains on %d GPUs %s (contiguous blocks of ~%d chains)" % (chains, len(devs), devs, blocks[0][1]))
+    return EngineGroup(made, blocks)
+
+
+def _result_mode(stream_results, *, return_engine, host_rand, external, has_planes, chains, n_out, model_ndim):
+    """How sample() hands over the ``n_out`` iterations it returns: "direct" / "windows" (streamed while the job runs,
+    _ResultStreamer) or None (copied when the job is over)."""
+    mode = {True: "direct", False: None, None: None}.get(stream_results, stream_results)
+    if mode not in (None, "direct", "windows"):
+        raise ValueError("stream_results must be True / 'direct', 'windows' or False")
+    if stream_results is True:
+        if chains * n_out * (model_ndim * 8 + 82) < _STREAM_MIN_BYTES:
+            mode = None          # a result of a few MiB: pinning twelve arrays and a helper thread cost more than one copy
+        elif return_engine:
+            mode = "windows"     # whoever keeps the engine reads the draws where diagnostics want them: in HBM (an explicit "direct" is honoured)
+    if host_rand or external or n_out <= 0 or not has_planes:
+        # jobs that launch per iteration (a host step_rand) or per tick (a torch / Python callable) never call the
+        # streamer: their results are copied when the job is over, whatever was asked for
+        mode = None
+    return mode
+
+
+def _launch_schedule(n_total, launch_iters, slots, per_dev, wide, external):
+    """``per_launch`` of _run_job: ``launch_iters`` if the caller gave it; otherwise from ``slots`` (resident wavefront
+    slots of the sampling kernel on one GPU; 0 / None: not reported), ``per_dev`` (chains per GPU), ``wide`` (general
+    kernels) and ``external`` (a torch / Python callable density, driven in ticks).
+
+    One launch for the whole job by default: every launch ends with a tail in which the chains with the longest trees run
+    alone (ragged targets: DESIGN.md section 6), so fewer, longer launches are faster -- except when the chains outnumber
+    the resident wavefront slots. Only a few times over: whole-job launches would run in a few job-long rounds with the
+    last one part empty, while in segments of 100 iterations the engine's sub-block streams keep the slots filled across
+    segment boundaries (+22 % at 8 192 x d=128). Many times over: a launch is also the granularity of Ctrl-C for the
+    chains whose wavefronts have not started yet (a workgroup that starts under a stop request does nothing: interrupting
+    ONE job-long launch of 20 rounds of residency would return no draw at all), so the job is cut into launches of 500
+    iterations -- few enough that the per-launch tail of ragged targets stays small."""
+    if launch_iters:
+        return int(launch_iters)
+    if external:
+        return max(n_total, 1)   # ticks: chains never wait for each other inside one request
+    per_launch = max(1, min(n_total, 4000))
+    if slots and slots < per_dev < 6 * slots:
+        return min(per_launch, 100)
+    if slots and per_dev >= 6 * slots:
+        # (round 5) the engine chooses the LDS plan of a launch when it is enqueued, from iteration 200 on and from what
+        # the running chains report (it ignores reports from the first 100): four launches of 100 let the choice settle
+        # by iteration 300, the rest of the job runs in launches of 500
+        return [100, 100, 100, 100, 500] if per_launch >= 500 else per_launch
+    if not slots and wide:
+        return min(per_launch, 200)   # general kernels (one workgroup per chain, a few hundred resident): same reason
+    return per_launch
+
+
+def _collect_results(step, eng, streamed, lo, n_done, chains, model_ndim):
+    """(trace[chains, n, ndim], stats[name][chains, n, 1]) of the iterations [lo, n_done): views of the streamed arrays
+    (an interrupted job returns the iterations every chain completed: a prefix of them), a copy from the engine, or empty."""
+    n_out = max(n_done - lo, 0)
+    dtypes = step.stats_dtypes[0].items()
+    if n_out > 0 and streamed is not None:
+        trace = streamed.trace if n_out == streamed.n_out else streamed.trace[:, :n_out]
+        return trace, {name: streamed.stats[name][:, :n_out, None].astype(dtype, copy=False) for name, dtype in dtypes}
+    if n_out > 0:
+        trace, raw = eng.trace(lo, n_out), step._stats_from_engine(eng, lo, n_out)
+        return trace, {name: raw[name][:, :, None].astype(dtype) for name, dtype in dtypes}
+    return np.zeros((chains, 0, model_ndim)), {name: np.zeros((chains, 0, 1), dtype=dtype) for name, dtype in dtypes}
+
+
+def _write_back_step_state(step, eng, tune, n_total, n_done, interrupted, chains):
+    """Leave the step object as the reference's sequential driver leaves it: state of the LAST chain."""
+    if not interrupted:
+        step.tune = False if n_total > 0 else step.tune
+    elif n_done > 0:
+        step.tune = n_done <= tune          # stop_tuning() happens at iteration index `tune` (sampling.py:510-511)
+    step.iter_count = n_done
+    step.step_adapt._pull(eng, chains - 1)
+    step.potential._pull(eng, chains - 1)
+    ct = eng.counters()
+    step._samples_after_tune += int(ct[:, _abi.CT_SAMPLES_AFTER_TUNE].sum())
+    step._num_divs_sample += int(ct[:, _abi.CT_DIVS_AFTER_TUNE].sum())
+    if hasattr(step, "_reached_max_treedepth"):
+        step._reached_max_treedepth += int(ct[:, _abi.CT_REACHED_MAX_TREEDEPTH].sum())
+    if n_done > tune:
+        tail = eng.stat_f64(_abi.STAT_ACCEPT, tune, n_done - tune)
+        step.step_adapt._tuned_stats = list(tail[chains - 1])
+
+
 def sample(logp_dlogp_func, model_ndim=None, draws=1000, tune=1000, step=None, init="auto", chains=None,
            cores=None, start=None, progressbar=True, random_seed=None, discard_tuned_samples=True,
            chain_idx=0, callback=None, mp_ctx=None, pickle_backend="pickle", size=None, device=None, devices=None,
@@ -368,11 +488,12 @@ def sample(logp_dlogp_func, model_ndim=None, draws=1000, tune=1000, step=None, i
     (lmc_engine_attach_trace) and every launch's statistics are copied under the launches that follow
     (lmc_engine_copy_window_async); "windows" -- the trace stays in HBM and is copied window by window like the statistics;
     False -- everything stays on the device until the job is over, then one blocking copy. The same arrays bit for bit
-    (tests/test_gpu_round6.py).
+    (test_streamed_results_equal_the_copy_after_the_job).
     """
     if model_ndim is None:
         model_ndim = size if size is not None else getattr(logp_dlogp_func, "d", None)
     target = require_device_target(logp_dlogp_func, model_ndim)
+    external = target.family == _abi.TARGET_EXTERNAL
     gpu_cap = cores                # the caller's own `cores` (None = not given) caps the number of GPUs
     if cores is None:
         cores = min(4, os.cpu_count() or 1)
@@ -391,22 +512,13 @@ def sample(logp_dlogp_func, model_ndim=None, draws=1000, tune=1000, step=None, i
             step = step_
         if start is None:
             start = start_
-    if isinstance(start, (list, tuple)):   # one start point per chain (sampling.py:161-164 accepts a list)
-        if len(start) != chains:
-            raise ValueError("start list must have one entry per chain")
-        start = np.stack([np.asarray(x, dtype="d") for x in start])
-    start = np.asarray(start, dtype="d")
-    if start.ndim == 1:   # same start for every chain (sampling.py:163-164)
-        starts = np.broadcast_to(start, (chains, model_ndim))
-    else:
-        starts = start
-        if starts.shape != (chains, model_ndim):
-            raise ValueError("start must have shape (model_ndim,) or (chains, model_ndim)")
+    starts = _start_points(start, chains, model_ndim)
 
-    n_total = int(tune) + int(draws)
+    tune, n_total = int(tune), int(tune) + int(draws)
+    lo = tune if discard_tuned_samples else 0   # sampling.py:473-476
 
     def _probe_slots():   # resident wavefront slots of this job's sampling kernel on one GPU (a one-chain engine knows)
-        if target.family == _abi.TARGET_EXTERNAL:
+        if external:
             return chains + 1     # a host / torch callable is evaluated on one device: no automatic fan-out
         probe = step._make_engine(1, device=0)
         try:
@@ -415,77 +527,31 @@ def sample(logp_dlogp_func, model_ndim=None, draws=1000, tune=1000, step=None, i
             probe.close()
 
     devs = _resolve_devices(devices, device, gpu_cap, chains, _probe_slots)
-    if len(devs) == 1:
-        eng = step._make_engine(chains, device=devs[0])
-    else:
-        from .distributed import chain_block
-        from .engine import EngineGroup
-
-        blocks = [chain_block(chains, k, len(devs)) for k in range(len(devs))]
-        made = []
-        try:
-            for dv, (b_lo, b_hi) in zip(devs, blocks):
-                made.append(step._make_engine(b_hi - b_lo, device=dv))
-        except BaseException:
-            for e_ in made:
-                e_.close()
-            raise
-        eng = EngineGroup(made, blocks)
-        _log.info("Sampling %d chains on %d GPUs %s (contiguous blocks of ~%d chains)" % (chains, len(devs), devs, blocks[0][1]))
+    eng = _make_engines(step, chains, devs)
     try:
         eng.seed(seeds)                       # np.random.seed(random_seed[i]) per chain (sampling.py:496-497)
         eng.set_position(np.ascontiguousarray(starts))
         if keep_moments:
             eng.keep_moments(True)
         eng.reset_tuning()                    # step.reset_tuning(); iter_count = 0 (sampling.py:503-509)
-        lo = int(tune) if discard_tuned_samples else 0   # sampling.py:473-476
         host_rand = getattr(step, "_host_step_rand", lambda: None)() is not None
         # Streamed results (the default): the arrays the caller gets are pinned while the first launches run, the sampling
         # kernel writes the draws straight into them ("direct") and every launch's statistics are copied under the launches
-        # that follow (_ResultStreamer). Not for jobs that launch per iteration (a host step_rand) or per tick (a torch /
-        # Python callable): their results are copied when the job is over.
-        mode = {True: "direct", False: None, None: None}.get(stream_results, stream_results)
-        if mode not in (None, "direct", "windows"):
-            raise ValueError("stream_results must be True / 'direct', 'windows' or False")
-        if host_rand or target.family == _abi.TARGET_EXTERNAL or n_total - lo <= 0 or not hasattr(step, "_result_planes"):
-            mode = None
-        if return_engine and stream_results is True:
-            mode = "windows"     # whoever keeps the engine reads the draws where diagnostics want them: in HBM (an explicit "direct" is honoured)
-        if stream_results is True and chains * (n_total - lo) * (model_ndim * 8 + 82) < _STREAM_MIN_BYTES:
-            mode = None          # a result of a few MiB: pinning twelve arrays and a helper thread cost more than one copy
+        # that follow (_ResultStreamer).
+        mode = _result_mode(stream_results, return_engine=return_engine, host_rand=host_rand, external=external,
+                            has_planes=hasattr(step, "_result_planes"), chains=chains, n_out=n_total - lo, model_ndim=model_ndim)
         eng.reserve(max(n_total, 1), keep_trace=mode != "direct", trace_begin=min(lo, max(n_total - 1, 0)))
-        # one launch for the whole job unless asked otherwise: every launch ends with a tail in which the chains with
-        # the longest trees run alone (ragged targets: DESIGN.md section 6), so fewer, longer launches are faster
-        per_launch = int(launch_iters) if launch_iters else max(1, min(n_total, 4000))
-        if not launch_iters:
-            # ...except when the chains outnumber the resident wavefront slots. Only a few times over: whole-job launches
-            # would run in a few job-long rounds with the last one part empty, while in segments of 100 iterations the
-            # engine's sub-block streams keep the slots filled across segment boundaries (+22 % at 8 192 x d=128).
-            # Many times over: a launch is also the granularity of Ctrl-C for the chains whose wavefronts have not started
-            # yet (a workgroup that starts under a stop request does nothing: interrupting ONE job-long launch of 20 rounds of
-            # residency would return no draw at all), so the job is cut into launches of 500 iterations -- few enough that
-            # the per-launch tail of ragged targets stays small.
-            slots = eng.resident_chains()
-            per_dev = -(-chains // len(devs))     # what one GPU holds
-            if slots and slots < per_dev < 6 * slots:
-                per_launch = min(per_launch, 100)
-            elif slots and per_dev >= 6 * slots:
-                # (round 5) the engine chooses the LDS plan of a launch when it is enqueued, from iteration 200 on and from what
-                # the running chains report (it ignores reports from the first 100): four launches of 100 let the choice settle
-                # by iteration 300, the rest of the job runs in launches of 500
-                per_launch = [100, 100, 100, 100, 500] if per_launch >= 500 else per_launch
-            elif not slots and getattr(getattr(eng, "engines", [eng])[0], "wide", False):
-                per_launch = min(per_launch, 200)   # general kernels (one workgroup per chain, a few hundred resident): same reason
-        if target.family == _abi.TARGET_EXTERNAL and not launch_iters:
-            per_launch = max(n_total, 1)   # ticks: chains never wait for each other inside one request
+        slots = None if launch_iters else eng.resident_chains()
+        wide = getattr(getattr(eng, "engines", [eng])[0], "wide", False)
+        per_launch = _launch_schedule(n_total, launch_iters, slots, -(-chains // len(devs)), wide, external)
         streamer = None
         if mode is not None:
             streamer = _ResultStreamer(eng, chains, n_total - lo, lo, model_ndim, step._result_planes(), direct=mode == "direct")
         try:
             if host_rand:
-                n_done, interrupted = _run_job_host_step_rand(eng, step, int(tune), n_total, progressbar, callback)
+                n_done, interrupted = _run_job_host_step_rand(eng, step, tune, n_total, progressbar, callback)
             else:
-                n_done, interrupted = _run_job(eng, int(tune), n_total, per_launch, progressbar, callback,
+                n_done, interrupted = _run_job(eng, tune, n_total, per_launch, progressbar, callback,
                                                on_enqueued=streamer.window if streamer is not None else None,
                                                before_enqueue=streamer.before_launch if streamer is not None else None)
         except BaseException:
@@ -499,36 +565,8 @@ def sample(logp_dlogp_func, model_ndim=None, draws=1000, tune=1000, step=None, i
             raise
         streamed = streamer.finish() if streamer is not None else None
         raise_for_status(eng.status())
-
-        n_out = max(n_done - lo, 0)
-        if n_out > 0 and streamed is not None:
-            # (an interrupted job returns the iterations every chain completed: a prefix of the arrays)
-            trace = streamed.trace if n_out == streamed.n_out else streamed.trace[:, :n_out]
-            stats = {name: streamed.stats[name][:, :n_out, None].astype(dtype, copy=False) for name, dtype in step.stats_dtypes[0].items()}
-        elif n_out > 0:
-            trace = eng.trace(lo, n_out)
-            raw = step._stats_from_engine(eng, lo, n_out)
-            stats = {name: raw[name][:, :, None].astype(dtype) for name, dtype in step.stats_dtypes[0].items()}
-        else:
-            trace = np.zeros((chains, 0, model_ndim))
-            stats = {name: np.zeros((chains, 0, 1), dtype=dtype) for name, dtype in step.stats_dtypes[0].items()}
-
-        # leave the step object as the reference's sequential driver leaves it: state of the LAST chain
-        if not interrupted:
-            step.tune = False if n_total > 0 else step.tune
-        elif n_done > 0:
-            step.tune = n_done <= int(tune)          # stop_tuning() happens at iteration index `tune` (sampling.py:510-511)
-        step.iter_count = n_done
-        step.step_adapt._pull(eng, chains - 1)
-        step.potential._pull(eng, chains - 1)
-        ct = eng.counters()
-        step._samples_after_tune += int(ct[:, _abi.CT_SAMPLES_AFTER_TUNE].sum())
-        step._num_divs_sample += int(ct[:, _abi.CT_DIVS_AFTER_TUNE].sum())
-        if hasattr(step, "_reached_max_treedepth"):
-            step._reached_max_treedepth += int(ct[:, _abi.CT_REACHED_MAX_TREEDEPTH].sum())
-        if n_done > int(tune):
-            tail = eng.stat_f64(_abi.STAT_ACCEPT, int(tune), n_done - int(tune))
-            step.step_adapt._tuned_stats = list(tail[chains - 1])
+        trace, stats = _collect_results(step, eng, streamed, lo, n_done, chains, model_ndim)
+        _write_back_step_state(step, eng, tune, n_total, n_done, interrupted, chains)
     except BaseException:   # KeyboardInterrupt / SystemExit included: never leak the engine (its HBM, its streams)
         eng.close()
         raise

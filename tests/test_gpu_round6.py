@@ -161,6 +161,21 @@ def test_streamed_results_on_two_engines_and_after_an_interrupt():
         np.testing.assert_array_equal(got[1][k][:, :m], one[1][k][:, :m], err_msg=k)
 
 
+def test_host_step_rand_job_with_a_kept_engine_returns_its_draws():
+    """A Python step_rand (one launch per iteration: nothing is streamed) with return_engine=True, the default
+    stream_results and a result over the streaming threshold (256 chains x 200 draws x d=32: 17 MB) returns the draws the
+    job made -- the same arrays bit for bit as stream_results=False. (return_engine once turned streaming back on here; no
+    launch fed the streamer, and sample() returned its zeroed arrays.)"""
+    d, chains = 32, 256
+    tgt = T.StdNormal(d)
+    kw = dict(draws=200, tune=20, chains=chains, random_seed=12, progressbar=False, step_rand=lambda s: 0.9 * s)
+    trace, stats, eng = lmc.sample(tgt, d, return_engine=True, **kw)
+    eng.close()
+    assert chains * 200 * (d * 8 + 82) >= 8 << 20
+    _same((trace, stats), lmc.sample(tgt, d, stream_results=False, **kw))
+    assert np.any(trace != 0) and np.all(stats["tree_size"] > 0)
+
+
 def test_copy_window_async_runs_under_the_next_launch():
     """The C ABI itself: windows enqueued right behind their launches, destination pinned (lmc_host_alloc); the host is not
     blocked by the enqueue (it returns long before the launch it follows is over), the copies are complete after copy_wait(),

@@ -372,6 +372,186 @@ def test_result_streamer_orders_attach_launch_and_window_copies(monkeypatch, pin
             assert eng.calls.index(c) > eng.calls.index(("run", 100, c[1] if c[1] != 100 else 60, 60 if c[1] != 180 else 50))
 
 
+# ---- the decisions of sample(), without a device ---------------------------------------------------------------------------
+_SIZES = {"small": (4, 100, 3), "large": (256, 200, 32), "empty": (256, 0, 32)}   # (chains, n_out, model_ndim): 41 KB, 17 MB, 0
+# what sample() returns a job's results through when nothing stops streaming, by (stream_results, return_engine, size)
+_MODES = {
+    (True, False, "small"): None, (True, False, "large"): "direct", (True, False, "empty"): None,
+    (True, True, "small"): None, (True, True, "large"): "windows", (True, True, "empty"): None,
+    (False, False, "small"): None, (False, False, "large"): None, (False, False, "empty"): None,
+    (False, True, "small"): None, (False, True, "large"): None, (False, True, "empty"): None,
+    ("direct", False, "small"): "direct", ("direct", False, "large"): "direct", ("direct", False, "empty"): None,
+    ("direct", True, "small"): "direct", ("direct", True, "large"): "direct", ("direct", True, "empty"): None,
+    ("windows", False, "small"): "windows", ("windows", False, "large"): "windows", ("windows", False, "empty"): None,
+    ("windows", True, "small"): "windows", ("windows", True, "large"): "windows", ("windows", True, "empty"): None,
+}
+
+
+@pytest.mark.parametrize("stream_results", [True, False, "direct", "windows"])
+@pytest.mark.parametrize("return_engine", [False, True])
+@pytest.mark.parametrize("size", sorted(_SIZES))
+def test_result_mode_table(stream_results, return_engine, size):
+    """sampling._result_mode: the table above where streaming is possible; None wherever the job never calls a streamer (a
+    host step_rand launches per iteration, a torch / Python callable density per tick) or the step has no result planes --
+    also with return_engine=True, which once turned streaming back on there and returned zeroed arrays."""
+    import itertools
+
+    chains, n_out, ndim = _SIZES[size]
+    for host_rand, external, has_planes in itertools.product([False, True], repeat=3):
+        got = sampling._result_mode(stream_results, return_engine=return_engine, host_rand=host_rand, external=external,
+                                    has_planes=has_planes, chains=chains, n_out=n_out, model_ndim=ndim)
+        want = None if (host_rand or external or not has_planes) else _MODES[stream_results, return_engine, size]
+        assert got == want, (host_rand, external, has_planes)
+
+
+def test_result_mode_rejects_what_it_does_not_know():
+    for bad in ("sideways", "Direct", 2):
+        with pytest.raises(ValueError, match="stream_results must be"):
+            sampling._result_mode(bad, return_engine=False, host_rand=True, external=True, has_planes=False,
+                                  chains=4, n_out=0, model_ndim=3)
+
+
+def test_launch_schedule_branches():
+    """sampling._launch_schedule(n_total, launch_iters, slots, per_dev, wide, external): every branch, at its edges."""
+    S = sampling._launch_schedule
+    # the caller's launch_iters wins over everything, ticks included
+    assert S(2000, 64, 1024, 65536, True, False) == 64
+    assert S(2000, 64, None, 4, False, True) == 64
+    # a torch / Python callable density: the whole job in one request of ticks
+    assert S(2000, None, None, 4, False, True) == 2000
+    assert S(0, None, None, 4, False, True) == 1
+    # no residency reported: one launch for the whole job (at most 4000 iterations), 200 on the general kernels
+    assert S(2000, None, 0, 65536, False, False) == 2000
+    assert S(10000, None, None, 65536, False, False) == 4000
+    assert S(0, None, 0, 4, False, False) == 1
+    assert S(2000, None, None, 10, True, False) == 200
+    assert S(150, None, 0, 10, True, False) == 150
+    # the chains fit the resident slots: one launch (wide only counts without a reported residency)
+    assert S(2000, None, 1024, 1024, False, False) == 2000
+    assert S(2000, None, 1024, 10, True, False) == 2000
+    # a few times over: launches of 100
+    assert S(2000, None, 1024, 1025, False, False) == 100
+    assert S(2000, None, 1024, 6 * 1024 - 1, False, False) == 100
+    assert S(50, None, 1024, 2048, False, False) == 50
+    # many times over: four launches of 100, then 500 -- unless the whole job is shorter than 500 iterations
+    assert S(2000, None, 1024, 6 * 1024, False, False) == [100, 100, 100, 100, 500]
+    assert S(500, None, 1024, 65536, False, False) == [100, 100, 100, 100, 500]
+    assert S(499, None, 1024, 65536, False, False) == 499
+    assert S(0, None, 1024, 65536, False, False) == 1
+
+
+class _SampleFakeEngine(FakeEngine):
+    """FakeEngine + what sample() itself asks of an engine (every draw and statistic reads as zero)."""
+
+    def __init__(self, chains, dim):
+        super().__init__(chains=chains)
+        self.dim = dim
+
+    def seed(self, seeds):
+        pass
+
+    def set_position(self, q):
+        pass
+
+    def reset_tuning(self):
+        pass
+
+    def reserve(self, capacity, keep_trace=True, trace_begin=0):
+        self.calls.append(("reserve", capacity, keep_trace, trace_begin))
+
+    def resident_chains(self):
+        return 1024
+
+    def set_step_sizes(self, step_sizes):
+        self.calls.append(("step_sizes", None if step_sizes is None else len(step_sizes)))
+
+    def status(self):
+        return np.zeros(self.chains, dtype=np.int32)
+
+    def trace(self, lo, n):
+        return np.zeros((self.chains, n, self.dim))
+
+    def counters(self):
+        return np.zeros((self.chains, _abi.NUM_COUNTERS), dtype=np.int64)
+
+    def stat_f64(self, stat, lo, n):
+        return np.zeros((self.chains, n))
+
+    def close(self):
+        self.calls.append(("close",))
+
+
+class _SampleFakeStep:
+    """The step object as sample() uses it; ``step_rand`` = a host callable, or None (the device's own)."""
+
+    stats_dtypes = [{"tree_size": np.float64, "diverging": np.bool_}]
+
+    def __init__(self, eng, step_rand):
+        self.eng, self.step_rand = eng, step_rand
+        self.step_adapt = types.SimpleNamespace(_pull=lambda eng, chain: None)
+        self.potential = types.SimpleNamespace(_pull=lambda eng, chain: None)
+        self.tune, self._samples_after_tune, self._num_divs_sample = True, 0, 0
+
+    def _make_engine(self, chains, device=0):
+        assert chains == self.eng.chains
+        return self.eng
+
+    def _host_step_rand(self):
+        return self.step_rand
+
+    def _host_step_sizes(self, eng, tune):
+        return np.full(eng.chains, self.step_rand(0.5))
+
+    def _result_planes(self):
+        return []
+
+    def _stats_from_engine(self, eng, lo, n):
+        return {name: np.zeros((eng.chains, n)) for name in self.stats_dtypes[0]}
+
+
+@pytest.mark.parametrize("host_rand", [True, False])
+def test_kept_engine_streams_only_jobs_that_feed_the_streamer(monkeypatch, host_rand):
+    """sample(return_engine=True) with the default stream_results and a 17 MB result: a job that launches per iteration (a
+    host step_rand) creates no _ResultStreamer -- nothing would feed it, and its arrays would come back all zero -- while
+    the same job with the device's own step sizes streams its windows (trace kept in HBM for the caller's engine)."""
+    from littlemcmc_amd import targets as T
+
+    made = []
+
+    class NoStreamer:
+        def __init__(self, eng, chains, n_out, first, dim, planes, direct):
+            assert not host_rand, "a host step_rand job must not stream its results"
+            made.append(direct)
+
+        def window(self, first, n):
+            pass
+
+        def before_launch(self, first, n):
+            pass
+
+        def finish(self):
+            return None          # (as if the arrays could not be pinned: sample() copies from the engine)
+
+    monkeypatch.setattr(sampling, "_ResultStreamer", NoStreamer)
+    chains, d, tune, draws = 256, 32, 10, 200
+    eng = _SampleFakeEngine(chains, d)
+    step = _SampleFakeStep(eng, (lambda s: 0.9 * s) if host_rand else None)
+    trace, stats, got = sampling.sample(T.StdNormal(d), d, draws=draws, tune=tune, step=step, start=np.zeros(d), chains=chains,
+                                        devices=[0], progressbar=False, return_engine=True)
+    assert got is eng and ("close",) not in eng.calls
+    assert trace.shape == (chains, draws, d) and stats["tree_size"].shape == (chains, draws, 1)
+    assert stats["diverging"].dtype == np.bool_
+    assert eng.calls[0] == ("reserve", tune + draws, True, tune)              # the trace stays in HBM either way
+    runs = [c for c in eng.calls if c[0] == "run"]
+    if host_rand:
+        assert made == [] and len(runs) == tune + draws                       # one launch per iteration
+        assert eng.calls[-1] == ("step_sizes", None)                          # handed back without the override
+    else:
+        assert made == [False]                                                # "windows"
+        assert runs == [("run", tune, 0, tune + draws)]
+    assert step.tune is False and step.iter_count == tune + draws
+
+
 def test_pinned_arrays_own_whole_pages_and_register_where_they_are_told():
     """engine.pinned_empty (no GPU: a stand-in for the two library calls): the block handed to lmc_host_register starts on a
     page boundary, spans whole pages and covers the array -- so no two pinned arrays share a page, whatever their size --;

@@ -41,12 +41,7 @@ def kernel_only():
         eng.set_position(start)
         eng.reset_tuning()
         eng.reserve(tune + draws, keep_trace=True, trace_begin=tune)
-        slots = eng.resident_chains()
-        per = max(1, min(tune + draws, 4000))
-        if slots and slots < chains < 6 * slots:
-            per = 100
-        elif slots and chains >= 6 * slots:
-            per = [100, 100, 100, 100, 500]
+        per = sampling._launch_schedule(tune + draws, None, eng.resident_chains(), chains, eng.wide, False)
         eng.synchronize()
         t0 = time.perf_counter()
         sampling._run_job(eng, tune, tune + draws, per, False)
