@@ -145,7 +145,10 @@ typedef struct lmc_tuning {
     int32_t dense_cache_rows_p1;  /* rows of the matrix a dense kernel caches in LDS, PLUS ONE (LMC_DENSE_CACHE_ROWS) */
     int32_t dense_lds_slots_p1;   /* leading tree slots a dense kernel keeps in LDS, PLUS ONE (LMC_DENSE_LDS_SLOTS) */
     int32_t chol_hbm;             /* 1: FullAdapt's refresh factorises through HBM at every size (LMC_CHOL_HBM) */
-    int32_t reserved[3];          /* must be 0 */
+    int32_t leaf_group;           /* NUTS tree build of the one-wave sampling kernels of <= 2 elements per lane: 2 = leaf pairs,
+                                   * 4 = leaf quads (the default), 0 = the engine decides; other shapes always build from pairs.
+                                   * Results do not depend on it (LMC_LEAF_GROUP) */
+    int32_t reserved[2];          /* must be 0 */
 } lmc_tuning;
 
 /* Constructor arguments of the step method: BaseHMC.__init__ (base_hmc.py:32-126) +
@@ -324,6 +327,9 @@ int lmc_engine_run_streams(lmc_engine* e, void** streams, int32_t capacity);
 /* The LDS plan (LMC_LDS_PLAN_SHALLOW / _DEEP) of the most recent lmc_engine_run() launch; 0 before the first launch and for
  * engines whose kernels have one plan only. lmc_engine_run_lds_bytes() reports the bytes of that launch. */
 int32_t lmc_engine_last_run_plan(lmc_engine* e);
+/* The leaf-group width of the NUTS tree build the most recent lmc_engine_run() launch ran (2 = leaf pairs, 4 = leaf quads;
+ * lmc_tuning.leaf_group); 0 before the first launch and for kernels that do not build trees in groups. */
+int32_t lmc_engine_last_run_leaf_group(lmc_engine* e);
 
 /* ---- results (synchronise the stream). dst shapes: trace [chains][n_iters][dim]; stats [chains][n_iters] */
 int lmc_engine_get_trace(lmc_engine* e, double* dst, int64_t iter_begin, int64_t n_iters);

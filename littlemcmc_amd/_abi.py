@@ -39,7 +39,8 @@ class Tuning(C.Structure):
 
     _fields_ = [("sub_blocks", C.c_int32), ("force_general", C.c_int32), ("general_team", C.c_int32), ("run_ns", C.c_int32),
                 ("run_w", C.c_int32), ("dense_coop_off", C.c_int32), ("dense_cache_rows_p1", C.c_int32),
-                ("dense_lds_slots_p1", C.c_int32), ("chol_hbm", C.c_int32), ("reserved", C.c_int32 * 3)]
+                ("dense_lds_slots_p1", C.c_int32), ("chol_hbm", C.c_int32), ("leaf_group", C.c_int32),
+                ("reserved", C.c_int32 * 2)]
 
 
 class Config(C.Structure):
@@ -135,6 +136,7 @@ _SIGNATURES = {
     "lmc_engine_run": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int32]),
     "lmc_engine_run_streams": (C.c_int, [_P, _P, C.c_int32]),
     "lmc_engine_last_run_plan": (C.c_int32, [_P]),
+    "lmc_engine_last_run_leaf_group": (C.c_int32, [_P]),
     "lmc_engine_copy_window_async": (C.c_int, [_P, C.POINTER(WindowDst), C.c_int64, C.c_int64]),
     "lmc_engine_copy_wait": (C.c_int, [_P]),
     "lmc_host_alloc": (_P, [C.c_uint64]),

@@ -313,6 +313,7 @@ struct lmc_engine {
     int lds_plan_wanted = 0;                          // lds_plan once a run-time compiled density has handed over its plan-1 kernel
     int plan_now = 0;                                 // the plan of the launches being enqueued (lds_plan == 2: follows the tree-size hint with hysteresis)
     int plan_last = -1;                               // the plan the most recent lmc_engine_run() actually launched with (-1: nothing launched yet)
+    int leaf_group = 2;                               // NUTS tree build of the sampling kernel (lmc_sampler.hpp: run_kernel<.., G>): 2 pairs, 4 quads
     bool wide = false;          // the general kernels (lmc_wide.hpp): one chain = 16 wavefronts, dpad = 1024 * ns -- model_ndim > 1024,
                                 // dense matrices beyond 256 dimensions, float64 adaptive diagonals
     double* init_diag64 = nullptr;   // [C][dpad] wide: the initial diagonal in float64
@@ -759,8 +760,10 @@ int lmc_engine_create(const lmc_config* cfg, lmc_engine** out) {
     if (cfg->chains < 1 || cfg->dim < 1) return fail(nullptr, LMC_ERR_INVALID, "chains and dim must be >= 1");
     if (cfg->lds_plan < LMC_LDS_PLAN_AUTO || cfg->lds_plan > LMC_LDS_PLAN_DEEP)
         return fail(nullptr, LMC_ERR_INVALID, "unknown lds_plan %d", cfg->lds_plan);
-    if (cfg->reserved0 != 0 || cfg->tuning.reserved[0] != 0 || cfg->tuning.reserved[1] != 0 || cfg->tuning.reserved[2] != 0)
+    if (cfg->reserved0 != 0 || cfg->tuning.reserved[0] != 0 || cfg->tuning.reserved[1] != 0)
         return fail(nullptr, LMC_ERR_INVALID, "reserved fields of lmc_config must be 0");
+    if (cfg->tuning.leaf_group != 0 && cfg->tuning.leaf_group != 2 && cfg->tuning.leaf_group != 4)
+        return fail(nullptr, LMC_ERR_INVALID, "unknown leaf_group %d (0, 2 or 4)", cfg->tuning.leaf_group);
     if (cfg->potential < LMC_POT_DIAG_ADAPT || cfg->potential > LMC_POT_FULL_F64)
         return fail(nullptr, LMC_ERR_INVALID, "unknown potential %d", cfg->potential);
     if (cfg->mass_f64 && cfg->potential > LMC_POT_DIAG && cfg->potential != LMC_POT_FULL_ADAPT)
@@ -896,6 +899,13 @@ int lmc_engine_create(const lmc_config* cfg, lmc_engine** out) {
     // granule taken as 1280 B -- measured: 12 800 B per wave keeps 12 waves/CU, 12 960 B does not); behind it the tail
     // (MT19937 state, team exchange). The rest of the stack goes to the chain's scratch row.
     int nlds = 1;
+    // leaf quads where run_leaf_group allows them unless tuning.leaf_group pins pairs; a run-time compiled density has its default
+    e->leaf_group = (!wide && run_leaf_group(e->run_ns, e->run_w) == 4 && cfg->tuning.leaf_group != 2) ? 4 : 2;
+    // kernels only, and the counter-based momentum stream its own default instantiation (the LDS sizes below must be those of
+    // the kernel that runs)
+    if ((cfg->target_family == LMC_TARGET_USER && !kUserCompiledIn) || cfg->rng_mode == LMC_RNG_PHILOX)
+        e->leaf_group = run_leaf_group(e->run_ns, e->run_w);
+    const int lg = e->leaf_group;
     if (wide) {
         e->nlds = 1;
         e->lds_bytes = wide_lds_bytes(e->dpad);
@@ -903,15 +913,15 @@ int lmc_engine_create(const lmc_config* cfg, lmc_engine** out) {
         const int waves_per_cu = 4 * run_waves_per_simd(e->run_ns, e->run_w);
         const int blocks_per_cu = waves_per_cu / e->run_w > 0 ? waves_per_cu / e->run_w : 1;
         const long budget = (163840L / blocks_per_cu) / 1280 * 1280 - lds_tail_doubles(e->run_w) * 8L;
-        if (pair_min_doubles(e->run_ns, e->run_w) * 8L > budget)
+        if (pair_min_doubles(e->run_ns, e->run_w, 0, lg) * 8L > budget)
             return bail(fail(nullptr, LMC_ERR_INVALID, "the sampling kernel's LDS plan does not fit the budget"));
         nlds = cfg->lds_levels > 0 ? cfg->lds_levels : 1;
         if (cfg->lds_levels <= 0)
-            while (nlds < max_levels && pair_total_doubles(e->run_ns, e->run_w, nlds + 1) * 8L <= budget) ++nlds;
+            while (nlds < max_levels && pair_total_doubles(e->run_ns, e->run_w, nlds + 1, 0, lg) * 8L <= budget) ++nlds;
         if (nlds > max_levels) nlds = max_levels;
         if (nlds < 1) nlds = 1;
         e->nlds = nlds;
-        e->lds_bytes = pair_total_doubles(e->run_ns, e->run_w, nlds) * 8;
+        e->lds_bytes = pair_total_doubles(e->run_ns, e->run_w, nlds, 0, lg) * 8;
         // The deep-tree plan of the one-wave kernels (lmc_sampler.hpp: PairLds<NS, 1, 1>, run_kernel's kDynPlan): MT19937 used in
         // place, one cold slot (none at NS = 4) in LDS, and the room that frees holds stack level 2. Same budget per wave (the
         // generator's 2.5 KB included, since it is not in LDS under this plan). By default the engine picks the plan of every
@@ -922,11 +932,11 @@ int lmc_engine_create(const lmc_config* cfg, lmc_engine** out) {
         e->lds_bytes1 = 0;
         e->lds_plan = 0;
         const long budget1 = (163840L / blocks_per_cu) / 1280 * 1280;
-        if (e->run_w == 1 && run_mt_in_lds(1) && cfg->lds_levels <= 0 && pair_min_doubles(e->run_ns, 1, 1) * 8L <= budget1) {
+        if (e->run_w == 1 && run_mt_in_lds(1) && cfg->lds_levels <= 0 && pair_min_doubles(e->run_ns, 1, 1, lg) * 8L <= budget1) {
             int n1 = 1;
-            while (n1 < max_levels && pair_total_doubles(e->run_ns, 1, n1 + 1, 1) * 8L <= budget1) ++n1;
+            while (n1 < max_levels && pair_total_doubles(e->run_ns, 1, n1 + 1, 1, lg) * 8L <= budget1) ++n1;
             e->nlds1 = n1;
-            e->lds_bytes1 = pair_total_doubles(e->run_ns, 1, n1, 1) * 8;
+            e->lds_bytes1 = pair_total_doubles(e->run_ns, 1, n1, 1, lg) * 8;
             e->lds_plan = cfg->lds_plan == LMC_LDS_PLAN_SHALLOW ? 0 : cfg->lds_plan == LMC_LDS_PLAN_DEEP ? 1 : 2;
             if (e->nlds1 <= e->nlds) e->lds_plan = 0;   // nothing gained: the plan would only move the generator out
             if (cfg->rng_mode == LMC_RNG_PHILOX) e->lds_plan = 0;   // (instantiated on the parity stream)
@@ -1178,6 +1188,9 @@ int lmc_engine_occupancy(lmc_engine* e, int32_t* resident_chains, int32_t* waves
                                                hipFuncAttributeMaxDynamicSharedMemorySize, run_lds));          \
             HIP_TRY(e, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, run_kernel<NSV, WV, T, 1>, block, \
                                                                     static_cast<size_t>(run_lds)));            \
+        } else if (e->leaf_group != run_leaf_group(NSV, WV)) {                                                 \
+            HIP_TRY(e, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, run_kernel<NSV, WV, T, 0, 0, 2>,  \
+                                                                    block, static_cast<size_t>(run_lds)));     \
         } else {                                                                                               \
             if (run_lds > 64 * 1024)                                                                           \
                 HIP_TRY(e, hipFuncSetAttribute(reinterpret_cast<const void*>(&run_kernel<NSV, WV, T>),         \
@@ -1206,6 +1219,10 @@ int32_t lmc_engine_run_lds_bytes(lmc_engine* e) {
     return sampling_lds_bytes(e, e->plan_last >= 0 ? e->plan_last : e->plan_now);   // the launch that ran, not the one that may come
 }
 
+int32_t lmc_engine_last_run_leaf_group(lmc_engine* e) {
+    if (!e || e->plan_last < 0 || e->cfg.kind != LMC_KIND_NUTS || e->wide || e->cfg.potential >= LMC_POT_FULL || e->cfg.target_family == LMC_TARGET_EXTERNAL) return 0;
+    return e->leaf_group;
+}
 int32_t lmc_engine_last_run_plan(lmc_engine* e) {
     if (!e || e->plan_last < 0 || e->wide || e->cfg.potential >= LMC_POT_FULL || e->cfg.target_family == LMC_TARGET_EXTERNAL) return 0;
     return e->plan_last == 1 ? LMC_LDS_PLAN_DEEP : LMC_LDS_PLAN_SHALLOW;
@@ -2032,7 +2049,10 @@ int lmc_engine_run(lmc_engine* e, int64_t n_tune, int64_t iter_begin, int32_t n_
     HIP_TRY(e, order_sub_blocks_after_main(e));
 #define RUN_PLAN1(NSV, WV, T)                                                                                  \
     if constexpr (WV == 1) {                                                                                   \
-        LMC_LAUNCH((run_kernel<NSV, 1, T, 0, 1>), grid, block, run_lds, st, e->A, P, e->tparams);              \
+        if (e->leaf_group != run_leaf_group(NSV, 1))                                                           \
+            LMC_LAUNCH((run_kernel<NSV, 1, T, 0, 1, 2>), grid, block, run_lds, st, e->A, P, e->tparams);       \
+        else                                                                                                   \
+            LMC_LAUNCH((run_kernel<NSV, 1, T, 0, 1>), grid, block, run_lds, st, e->A, P, e->tparams);          \
     }
 #define RUN_ONE(NSV, WV, T)                                                                                    \
     if (!found && e->run_ns == NSV && e->run_w == WV) {                                                        \
@@ -2044,6 +2064,9 @@ int lmc_engine_run(lmc_engine* e, int64_t n_tune, int64_t iter_begin, int32_t n_
             LMC_LAUNCH((run_kernel<NSV, WV, T, 1>), grid, block, run_lds, st, e->A, P, e->tparams);            \
         } else if (plan == 1) {                                                                                \
             RUN_PLAN1(NSV, WV, T)                                                                              \
+        } else if (e->leaf_group != run_leaf_group(NSV, WV)) {                                                 \
+            if constexpr (WV == 1)   /* the pinned pair form (run_lds <= 64 KB at one wave) */                \
+                LMC_LAUNCH((run_kernel<NSV, 1, T, 0, 0, 2>), grid, block, run_lds, st, e->A, P, e->tparams);   \
         } else {                                                                                               \
             if (run_lds > 64 * 1024)                                                                           \
                 HIP_TRY(e, hipFuncSetAttribute(reinterpret_cast<const void*>(&run_kernel<NSV, WV, T>),         \

@@ -697,10 +697,16 @@ constexpr int kLevelScalDoubles = 96;   // 4 per parked level, levels < 24 (max_
 enum ColdSlot : int { kColdAold = 0, kColdPsum = 1, kColdOp = 2, kColdOq = 3, kColdOg = 4, kNumCold = 5 };
 constexpr int kNumColdSlots = kNumCold;
 
-template <int NS, int W = 1, int PL = 0>
+// Leaf-group width of the tree build: 2 = leaf PAIRS, 4 = leaf QUADS (one-wave kernels of at most two elements per lane, see
+// nuts_transition2). The quad form needs a reduction buffer of eight rows and no level-1 slot; the teams and NS = 4 have no
+// registers to spare for it.
+constexpr int run_leaf_group(int ns, int w) { return (w == 1 && ns <= 2) ? 4 : 2; }
+template <int NS, int W = 1, int PL = 0, int G = 2>
 struct PairLds {   // offsets in doubles from the start of the block's dynamic LDS; W waves share one plan
+    static_assert(G == 2 || (G == 4 && W == 1), "leaf quads exist for the one-wave kernels");
     static constexpr int DP = 64 * NS * W;
-    static constexpr int kRedWave = 64 * kRedValues;              // one reduction buffer per wave
+    static constexpr int kRedRows = G == 4 ? 8 : kRedValues;        // values one gather sums (lanes 8k+7)
+    static constexpr int kRedWave = 64 * kRedRows;                // one reduction buffer per wave
     static constexpr int kRedSize = (2 * DP > W * kRedWave) ? 2 * DP : W * kRedWave;   // also normals / sdot staging
     static constexpr int kExp = kRedSize;
     static constexpr int kXsum = kExp + kExpTableDoubles;         // team combine area (W > 1): 2 buffers x 8 sums x W waves
@@ -716,8 +722,17 @@ struct PairLds {   // offsets in doubles from the start of the block's dynamic L
     static_assert(PL == 0 || W == 1, "the deep-tree plan exists for one-wave kernels");
     static constexpr int kColdLds = PL == 1 ? (NS >= 4 ? 0 : (LMC_PAIR_COLD_LDS < 1 ? LMC_PAIR_COLD_LDS : 1))
                                             : (W >= 8 ? (LMC_PAIR_COLD_LDS < 2 ? LMC_PAIR_COLD_LDS : 2) : LMC_PAIR_COLD_LDS);
-    static constexpr int kL1 = kCold + kColdLds * DP;             // level 1: {lp, rp, q}
-    static constexpr int kL2 = kL1 + 3 * DP;                      // levels 2..nlds: {lp, rp, psum, q}
+    // G = 2: level 1 {lp, rp, q}. G = 4: a quad is a complete level-2 node, nothing is ever parked at level 1; the slot holds
+    // the proposal candidates q of the quad's leaves 0 and 1 instead (kQStage; NS = 1 under plan 1 keeps them in registers).
+    // Sizes (doubles; one wave, NS = 2, DP = 128): pair 384 (reduction) + 32 (exp) + 96 (scalars) + cold + 384 (level 1),
+    // quad 512 + 32 + 96 + cold + 256 (q0, q1): the same total. Plan 0 (3 cold): 1280 = 10 KB head + 4 KB per LDS level
+    // (+ 2.5 KB generator, nlds = 1 in the 12.5 KB a wave has at 12 waves / CU); plan 1 (1 cold): 1024 + 512 per level, nlds = 2:
+    // 12 KB of 12.5. NS = 1 (DP = 64, 16 waves / CU: 10 KB = 1280 doubles): plan 0 pair 512 + 192 (cold) + 192 (level 1) = 896,
+    // quad 640 + 192 + 128 (q0, q1) = 960, exactly what the 320-double generator leaves; plan 1 pair 512 + 64 + 192 = 768,
+    // quad 640 + 64 = 704, + 256 per level (nlds = 3 either way).
+    static constexpr int kQStage = (G == 4 && (NS >= 2 || PL == 0)) ? 2 : 0;
+    static constexpr int kL1 = kCold + kColdLds * DP;             // level 1: {lp, rp, q} (G = 2); staged q0, q1 (G = 4)
+    static constexpr int kL2 = kL1 + (G == 4 ? kQStage : 3) * DP; // levels 2..nlds: {lp, rp, psum, q}
     static constexpr int kMinDoubles = kL2;                       // head + cold + level 1: what the form needs at least
     static constexpr int kGlbLevels = (kNumCold - kColdLds) * DP; // scratch row: cold slots not in LDS, then levels > nlds
     __host__ __device__ static constexpr int total_doubles(int nlds) { return kL2 + (nlds > 1 ? (nlds - 1) * 4 * DP : 0); }
@@ -732,14 +747,21 @@ struct PairLds {   // offsets in doubles from the start of the block's dynamic L
 #else
 #define LMC_PAIR_SHAPES(X) X(1, 1) X(2, 1) X(4, 1) X(4, 2) X(4, 4)
 #endif
-constexpr int pair_min_doubles(int ns, int w, int plan = 0) {
-#define X(NSV, WV) if (ns == NSV && w == WV) return (plan == 1 && WV == 1) ? PairLds<NSV, 1, 1>::kMinDoubles : PairLds<NSV, WV, 0>::kMinDoubles;
+// g: the leaf-group width the kernel runs (4 only where run_leaf_group allows it)
+constexpr int pair_min_doubles(int ns, int w, int plan = 0, int g = 2) {
+#define X(NSV, WV) if (ns == NSV && w == WV) {                                                                               \
+        if (g == 4 && run_leaf_group(NSV, WV) == 4)                                                                          \
+            return plan == 1 ? PairLds<NSV, 1, 1, 4>::kMinDoubles : PairLds<NSV, 1, 0, 4>::kMinDoubles;                      \
+        return (plan == 1 && WV == 1) ? PairLds<NSV, 1, 1>::kMinDoubles : PairLds<NSV, WV, 0>::kMinDoubles; }
     LMC_PAIR_SHAPES(X)
 #undef X
     return 1 << 30;
 }
-constexpr int pair_total_doubles(int ns, int w, int nlds, int plan = 0) {
-#define X(NSV, WV) if (ns == NSV && w == WV) return (plan == 1 && WV == 1) ? PairLds<NSV, 1, 1>::total_doubles(nlds) : PairLds<NSV, WV, 0>::total_doubles(nlds);
+constexpr int pair_total_doubles(int ns, int w, int nlds, int plan = 0, int g = 2) {
+#define X(NSV, WV) if (ns == NSV && w == WV) {                                                                               \
+        if (g == 4 && run_leaf_group(NSV, WV) == 4)                                                                          \
+            return plan == 1 ? PairLds<NSV, 1, 1, 4>::total_doubles(nlds) : PairLds<NSV, 1, 0, 4>::total_doubles(nlds);      \
+        return (plan == 1 && WV == 1) ? PairLds<NSV, 1, 1>::total_doubles(nlds) : PairLds<NSV, WV, 0>::total_doubles(nlds); }
     LMC_PAIR_SHAPES(X)
 #undef X
     return 1 << 30;
@@ -757,7 +779,7 @@ struct PairCtx {
 };
 
 // ---- batched lane reductions through LDS ("transposed" reduction)
-template <int NS, int W = 1, int PL = 0>
+template <int NS, int W = 1, int PL = 0, int G = 2>
 __device__ __forceinline__ void red_put(const PairCtx& cx, int v, double x) {
     if constexpr (W == 1) ((lds_double*)cx.lds)[v * 64 + lane_id()] = x;
     else ((lds_double*)cx.lds)[v * 64 + lane_id() + cx.wave_red] = x;
@@ -767,7 +789,7 @@ __device__ __forceinline__ void red_put(const PairCtx& cx, int v, double x) {
 // Team (W > 1): every wave reduces its own buffer, lanes 8k+7 drop the wave's six sums into a double-buffered combine
 // area, ONE barrier, every wave adds the W partials in wave order (the same value in every wave). A wave can reach
 // the next-but-one reduction (same buffer) only after every wave has passed the barrier in between.
-template <int NS, int W = 1, int PL = 0>
+template <int NS, int W = 1, int PL = 0, int G = 2>
 __device__ __forceinline__ double red_gather(PairCtx& cx) {
     typedef double d2 __attribute__((ext_vector_type(2)));
     typedef __attribute__((address_space(3))) d2 lds_d2;
@@ -788,7 +810,7 @@ __device__ __forceinline__ double red_gather(PairCtx& cx) {
     s += dpp_f64<0x114>(s);
     if constexpr (W > 1) {
         const int lane = lane_id();
-        lds_double* xs = L + (PairLds<NS, W, PL>::kXsum + cx.xpar * (8 * W)) + (lane >> 3) * W;
+        lds_double* xs = L + (PairLds<NS, W, PL, G>::kXsum + cx.xpar * (8 * W)) + (lane >> 3) * W;
         if ((lane & 7) == 7) xs[cx.wave] = s;
         __syncthreads();
         double t = xs[0];
@@ -799,9 +821,9 @@ __device__ __forceinline__ double red_gather(PairCtx& cx) {
     }
     return s;
 }
-__device__ __forceinline__ int red_lane_init() {
+__device__ __forceinline__ int red_lane_init(int rows = kRedValues) {
     const int lane = lane_id();
-    const int row = lane < 8 * kRedValues ? lane : 0;   // rows beyond the buffer re-read row 0 (their sums are never used)
+    const int row = lane < 8 * rows ? lane : 0;   // rows beyond the buffer re-read row 0 (their sums are never used)
     return row * 8 + 2 * ((lane >> 2) & 3);
 }
 // any of the sums k in [k0, k0 + n) <= 0 ?
@@ -841,13 +863,13 @@ __device__ __forceinline__ ExpLanesConst exp_lanes_const() {
 #endif
     return c;
 }
-template <int NS, int W = 1, int PL = 0>
+template <int NS, int W = 1, int PL = 0, int G = 2>
 __device__ __forceinline__ double exp_lanes(const PairCtx& cx, const ExpLanesConst& c, double x) {
     const double kf = rint(x * c.inv);
     double r = __builtin_fma(-kf, c.hi, x);
     r = __builtin_fma(-kf, c.lo, r);
     const int ki = static_cast<int>(kf);
-    const double t = ((const lds_double*)cx.lds)[PairLds<NS, W, PL>::kExp + (ki & 31)];
+    const double t = ((const lds_double*)cx.lds)[PairLds<NS, W, PL, G>::kExp + (ki & 31)];
     double p = fma_sgpr_addend(r, c.c6, c.c5);
     p = fma_sgpr_addend(p, r, c.c4);
     p = fma_sgpr_addend(p, r, c.c3);
@@ -858,101 +880,101 @@ __device__ __forceinline__ double exp_lanes(const PairCtx& cx, const ExpLanesCon
 }
 
 // ---- cold slots and subtree-stack levels: LDS offsets are immediates, the scratch row takes what does not fit
-template <int NS, int W, int PL, int SLOT>
+template <int NS, int W, int PL, int G, int SLOT>
 __device__ __forceinline__ void cold_load(const PairCtx& cx, double (&x)[NS]) {
-    using L = PairLds<NS, W, PL>;
+    using L = PairLds<NS, W, PL, G>;
     if constexpr (SLOT < L::kColdLds) vload_as<NS>((lds_double*)cx.lds + (L::kCold + SLOT * L::DP), x);
     else vload_as<NS>((glb_double*)cx.glb + (SLOT - L::kColdLds) * L::DP, x);
 }
-template <int NS, int W, int PL, int SLOT>
+template <int NS, int W, int PL, int G, int SLOT>
 __device__ __forceinline__ void cold_store(const PairCtx& cx, const double (&x)[NS]) {
-    using L = PairLds<NS, W, PL>;
+    using L = PairLds<NS, W, PL, G>;
     if constexpr (SLOT < L::kColdLds) vstore_as<NS>((lds_double*)cx.lds + (L::kCold + SLOT * L::DP), x);
     else vstore_as<NS>((glb_double*)cx.glb + (SLOT - L::kColdLds) * L::DP, x);
 }
 // level 1 (always LDS): {lp, rp, q}
-template <int NS, int W = 1, int PL = 0>
+template <int NS, int W = 1, int PL = 0, int G = 2>
 __device__ __forceinline__ void level1_load(const PairCtx& cx, double (&lp)[NS], double (&rp)[NS], double (&ps)[NS]) {
-    using L = PairLds<NS, W, PL>;
+    using L = PairLds<NS, W, PL, G>;
     lds_double* b = (lds_double*)cx.lds + L::kL1;
     vload_as<NS>(b, lp); vload_as<NS>(b + L::DP, rp);
 #pragma unroll
     for (int s = 0; s < NS; ++s) ps[s] = lp[s] + rp[s];   // the very sum the pair formed (nuts.py:386)
 }
-template <int NS, int W = 1, int PL = 0>
+template <int NS, int W = 1, int PL = 0, int G = 2>
 __device__ __forceinline__ void level1_store(const PairCtx& cx, const double (&lp)[NS], const double (&rp)[NS], const double (&pq)[NS]) {
-    using L = PairLds<NS, W, PL>;
+    using L = PairLds<NS, W, PL, G>;
     lds_double* b = (lds_double*)cx.lds + L::kL1;
     vstore_as<NS>(b, lp); vstore_as<NS>(b + L::DP, rp); vstore_as<NS>(b + 2 * L::DP, pq);
 }
 // offset (doubles) of vector v of level j > nlds in the scratch row. Opaque to the optimiser on purpose: a
 // loop-invariant level (the peeled j = 2) would otherwise get its per-lane 64-bit address precomputed outside the pair
 // loop and kept in (spilled) registers; this way the access is scalar base + uniform offset + the lane-offset register
-template <int NS, int W = 1, int PL = 0>
+template <int NS, int W = 1, int PL = 0, int G = 2>
 __device__ __forceinline__ unsigned glb_level_offset(const PairCtx& cx, int j, int v) {
-    using L = PairLds<NS, W, PL>;
+    using L = PairLds<NS, W, PL, G>;
     unsigned off = L::kGlbLevels + static_cast<unsigned>(j - cx.nlds - 1) * (4u * L::DP) + static_cast<unsigned>(v) * L::DP;
     asm volatile("" : "+s"(off));
     return off;
 }
 // levels j >= 2: {lp, rp, psum, q}; vector index v in 0..3
-template <int NS, int W = 1, int PL = 0>
+template <int NS, int W = 1, int PL = 0, int G = 2>
 __device__ __forceinline__ void levelN_load(const PairCtx& cx, int j, int v, double (&x)[NS]) {
-    using L = PairLds<NS, W, PL>;
+    using L = PairLds<NS, W, PL, G>;
     int nl = cx.nlds;
     asm volatile("" : "+s"(nl));   // compared afresh (one s_cmp): hoisted, the loop-invariant test lives in a spilled lane mask
     if (j <= nl) vload_as<NS>((lds_double*)cx.lds + (L::kL2 + (j - 2) * 4 * L::DP + v * L::DP), x);
-    else vload_as<NS>((glb_double*)cx.glb + glb_level_offset<NS, W, PL>(cx, j, v), x);
+    else vload_as<NS>((glb_double*)cx.glb + glb_level_offset<NS, W, PL, G>(cx, j, v), x);
 }
-template <int NS, int W = 1, int PL = 0>
+template <int NS, int W = 1, int PL = 0, int G = 2>
 __device__ __forceinline__ void levelN_store(const PairCtx& cx, int j, int v, const double (&x)[NS]) {
-    using L = PairLds<NS, W, PL>;
+    using L = PairLds<NS, W, PL, G>;
     int nl = cx.nlds;
     asm volatile("" : "+s"(nl));
     if (j <= nl) vstore_as<NS>((lds_double*)cx.lds + (L::kL2 + (j - 2) * 4 * L::DP + v * L::DP), x);
-    else vstore_as<NS>((glb_double*)cx.glb + glb_level_offset<NS, W, PL>(cx, j, v), x);
+    else vstore_as<NS>((glb_double*)cx.glb + glb_level_offset<NS, W, PL, G>(cx, j, v), x);
 }
 // left-end momentum / proposal position of any level j >= 1
-template <int NS, int W = 1, int PL = 0>
+template <int NS, int W = 1, int PL = 0, int G = 2>
 __device__ __forceinline__ void level_load_lp(const PairCtx& cx, int j, double (&x)[NS]) {
-    if (j == 1) vload_as<NS>((lds_double*)cx.lds + PairLds<NS, W, PL>::kL1, x); else levelN_load<NS, W, PL>(cx, j, 0, x);
+    if (j == 1) vload_as<NS>((lds_double*)cx.lds + PairLds<NS, W, PL, G>::kL1, x); else levelN_load<NS, W, PL, G>(cx, j, 0, x);
 }
-template <int NS, int W = 1, int PL = 0>
+template <int NS, int W = 1, int PL = 0, int G = 2>
 __device__ __forceinline__ void level_load_q(const PairCtx& cx, int j, double (&x)[NS]) {
-    if (j == 1) vload_as<NS>((lds_double*)cx.lds + (PairLds<NS, W, PL>::kL1 + 2 * PairLds<NS, W, PL>::DP), x); else levelN_load<NS, W, PL>(cx, j, 3, x);
+    if (j == 1) vload_as<NS>((lds_double*)cx.lds + (PairLds<NS, W, PL, G>::kL1 + 2 * PairLds<NS, W, PL, G>::DP), x); else levelN_load<NS, W, PL, G>(cx, j, 3, x);
 }
-template <int NS, int W = 1, int PL = 0>
+template <int NS, int W = 1, int PL = 0, int G = 2>
 __device__ __forceinline__ void level_scal_put(const PairCtx& cx, int j, double w, double a, double pe, double plogp) {
     if (lane_id() == 0) {
-        lds_double* s = (lds_double*)cx.lds + (PairLds<NS, W, PL>::kScal + 4 * j) + (W > 1 ? cx.wave_scal : 0);
+        lds_double* s = (lds_double*)cx.lds + (PairLds<NS, W, PL, G>::kScal + 4 * j) + (W > 1 ? cx.wave_scal : 0);
         s[0] = w; s[1] = a; s[2] = pe; s[3] = plogp;
     }
 }
 // weights of level j only (the proposal's energy / log-density stay where they are until a node is parked or accepted)
-template <int NS, int W = 1, int PL = 0>
+template <int NS, int W = 1, int PL = 0, int G = 2>
 __device__ __forceinline__ void level_scal_get_wa(const PairCtx& cx, int j, double& w, double& a) {
-    const lds_double* s = (const lds_double*)cx.lds + (PairLds<NS, W, PL>::kScal + 4 * j) + (W > 1 ? cx.wave_scal : 0);
+    const lds_double* s = (const lds_double*)cx.lds + (PairLds<NS, W, PL, G>::kScal + 4 * j) + (W > 1 ? cx.wave_scal : 0);
     w = s[0]; a = s[1];
 }
 // scalars of a node parked at level j: weights from the caller; the proposal's {energy, log-density} from their source --
 // lane `elane` of (en, lp) when the proposal is a leaf of the current pair (src < 0: that lane stores them itself, no
 // cross-lane read), else copied from level src
-template <int NS, int W = 1, int PL = 0>
+template <int NS, int W = 1, int PL = 0, int G = 2>
 __device__ __forceinline__ void level_scal_park(const PairCtx& cx, int j, double w, double a, int src, int elane, double en, double lp) {
-    lds_double* s = (lds_double*)cx.lds + (PairLds<NS, W, PL>::kScal + 4 * j) + (W > 1 ? cx.wave_scal : 0);
+    lds_double* s = (lds_double*)cx.lds + (PairLds<NS, W, PL, G>::kScal + 4 * j) + (W > 1 ? cx.wave_scal : 0);
     const int lane = lane_id();
     if (src < 0) {
         if (lane == elane) { s[2] = en; s[3] = lp; }
     } else {
-        const lds_double* f = (const lds_double*)cx.lds + (PairLds<NS, W, PL>::kScal + 4 * src) + (W > 1 ? cx.wave_scal : 0);
+        const lds_double* f = (const lds_double*)cx.lds + (PairLds<NS, W, PL, G>::kScal + 4 * src) + (W > 1 ? cx.wave_scal : 0);
         const double pe = f[2], pl = f[3];
         if (lane == 0) { s[2] = pe; s[3] = pl; }
     }
     if (lane == 0) { s[0] = w; s[1] = a; }
 }
-template <int NS, int W = 1, int PL = 0>
+template <int NS, int W = 1, int PL = 0, int G = 2>
 __device__ __forceinline__ void level_scal_get(const PairCtx& cx, int j, double& w, double& a, double& pe, double& plogp) {
-    const lds_double* s = (const lds_double*)cx.lds + (PairLds<NS, W, PL>::kScal + 4 * j) + (W > 1 ? cx.wave_scal : 0);   // same address in every lane: LDS broadcast
+    const lds_double* s = (const lds_double*)cx.lds + (PairLds<NS, W, PL, G>::kScal + 4 * j) + (W > 1 ? cx.wave_scal : 0);   // same address in every lane: LDS broadcast
     w = s[0]; a = s[1]; pe = s[2]; plogp = s[3];
 }
 
@@ -987,7 +1009,7 @@ __device__ __forceinline__ void leapfrog_partial(TeamT& tm, const Target& tgt, c
 }
 
 // one cascade level: node a = {alp, arp, aps} (earlier), in-flight node {tl (left end), tps, right end velocity v}
-template <int NS, int W = 1, int PL = 0>
+template <int NS, int W = 1, int PL = 0, int G = 2>
 __device__ __forceinline__ double cascade_dots(PairCtx& cx, const double (&var)[NS], const double (&alp)[NS],
                                                const double (&arp)[NS], const double (&aps)[NS], const double (&tl)[NS],
                                                double (&tps)[NS], const double (&v)[NS]) {
@@ -1003,13 +1025,18 @@ __device__ __forceinline__ double cascade_dots(PairCtx& cx, const double (&var)[
         d4 = __builtin_fma(p2, varp, d4); d5 = __builtin_fma(p2, v[s], d5);
         tps[s] = ps;
     }
-    red_put<NS, W, PL>(cx, 0, d0); red_put<NS, W, PL>(cx, 1, d1); red_put<NS, W, PL>(cx, 2, d2);
-    red_put<NS, W, PL>(cx, 3, d3); red_put<NS, W, PL>(cx, 4, d4); red_put<NS, W, PL>(cx, 5, d5);
-    return red_gather<NS, W, PL>(cx);
+    red_put<NS, W, PL, G>(cx, 0, d0); red_put<NS, W, PL, G>(cx, 1, d1); red_put<NS, W, PL, G>(cx, 2, d2);
+    red_put<NS, W, PL, G>(cx, 3, d3); red_put<NS, W, PL, G>(cx, 4, d4); red_put<NS, W, PL, G>(cx, 5, d5);
+    return red_gather<NS, W, PL, G>(cx);
 }
 
 // On return the chain's row of A.q (qrow) holds the proposal; q is NOT updated (the caller reloads it).
-template <int NS, int PL, class Target, class TeamT>
+// G: the leaf-group width (run_leaf_group). G = 2 builds every subtree from leaf PAIRS. G = 4 builds subtrees of depth >= 2
+// from leaf QUADS: leaves 4k .. 4k+3 form a complete level-2 node, so its two level-0 merges and its level-1 merge are decided
+// inside the group -- one set of leaf scalars (energies, divergence ballot, weights) on lanes 15 / 31 / 47 / 63 for four
+// leaves, the eighteen sums of the group in three gathers issued back to back, and nothing parked at level 1. Every sum keeps
+// its per-lane FMA order and its summation tree and every uniform its place in the stream: the forms are bit-identical.
+template <int NS, int PL, int G, class Target, class TeamT>
 __device__ inline void nuts_transition2(TeamT& tm, const Target& tgt, const double (&var)[NS], RngState& rng,
                                         PairCtx& cx, double* qrow, const double (&q)[NS],
                                         const double (&p0)[NS], const double (&g0)[NS], double e0, double logp0,
@@ -1020,8 +1047,8 @@ __device__ inline void nuts_transition2(TeamT& tm, const Target& tgt, const doub
     // momentum sum and the extended end's momentum before the doubling are cold slots
     double cq[NS], cp[NS], cg[NS];
     vcopy(cq, q); vcopy(cp, p0); vcopy(cg, g0);
-    cold_store<NS, W, PL, kColdOq>(cx, q); cold_store<NS, W, PL, kColdOp>(cx, p0); cold_store<NS, W, PL, kColdOg>(cx, g0);
-    cold_store<NS, W, PL, kColdPsum>(cx, p0);
+    cold_store<NS, W, PL, G, kColdOq>(cx, q); cold_store<NS, W, PL, G, kColdOp>(cx, p0); cold_store<NS, W, PL, G, kColdOg>(cx, g0);
+    cold_store<NS, W, PL, G, kColdPsum>(cx, p0);
     bool c_right = true;                                    // which end {c*} is
     bool c_start = momentum_f32, o_start = momentum_f32;    // end still is the float32 start state
     double prop_e = e0, prop_logp = logp0;
@@ -1033,7 +1060,7 @@ __device__ inline void nuts_transition2(TeamT& tm, const Target& tgt, const doub
     // c_tot of the moment they were last merged and are brought to the current one only when a subtree is ACCEPTED: a
     // rejected subtree whose leaf moved the offset by more than ~745 would otherwise flush them to zero and the
     // acceptance statistic with them (0/0).
-    lds_double* tot = (lds_double*)cx.lds + PairLds<NS, W, PL>::kScal + (W > 1 ? cx.wave_scal : 0);
+    lds_double* tot = (lds_double*)cx.lds + PairLds<NS, W, PL, G>::kScal + (W > 1 ? cx.wave_scal : 0);
     if (lane_id() == 0) { tot[0] = 0.0; tot[1] = 0.0; tot[2] = 1.0; tot[3] = 0.0; }
     int depth = 0, n_leap = 0;
     bool diverging = false, turning = false, exhausted = true;
@@ -1082,7 +1109,7 @@ __device__ inline void nuts_transition2(TeamT& tm, const Target& tgt, const doub
                     const double f = exp_uniform(coff - x);
                     const int lane = lane_id();
                     if (lane >= 1 && lane < kLevelScalDoubles / 4) {   // the parked levels {w, a, ..}; slot 0 (totals) keeps its own offset
-                        lds_double* sc = (lds_double*)cx.lds + (PairLds<NS, W, PL>::kScal + 4 * lane) + (W > 1 ? cx.wave_scal : 0);
+                        lds_double* sc = (lds_double*)cx.lds + (PairLds<NS, W, PL, G>::kScal + 4 * lane) + (W > 1 ? cx.wave_scal : 0);
                         sc[0] = sc[0] * f; sc[1] = sc[1] * f;
                     }
                     coff = x;
@@ -1100,7 +1127,7 @@ __device__ inline void nuts_transition2(TeamT& tm, const Target& tgt, const doub
         const double x = -de;
         const double xn = dpp_f64<0x101>(x);                   // row_shl:1: lane l <- lane l+1
         const double arg = odd_lane ? (x - coff) : ((xn - coff) + fmin(xn, 0.0));
-        ev = exp_lanes<NS, W, PL>(cx, ec, arg);
+        ev = exp_lanes<NS, W, PL, G>(cx, ec, arg);
         return ok;
     };
 
@@ -1109,20 +1136,33 @@ __device__ inline void nuts_transition2(TeamT& tm, const Target& tgt, const doub
         const double eps = right ? step_size : -step_size;
         if (right != c_right) {   // the other end becomes the one that is extended
             double t[NS];
-            cold_load<NS, W, PL, kColdOq>(cx, t); cold_store<NS, W, PL, kColdOq>(cx, cq); vcopy(cq, t);
-            cold_load<NS, W, PL, kColdOp>(cx, t); cold_store<NS, W, PL, kColdOp>(cx, cp); vcopy(cp, t);
-            cold_load<NS, W, PL, kColdOg>(cx, t); cold_store<NS, W, PL, kColdOg>(cx, cg); vcopy(cg, t);
+            cold_load<NS, W, PL, G, kColdOq>(cx, t); cold_store<NS, W, PL, G, kColdOq>(cx, cq); vcopy(cq, t);
+            cold_load<NS, W, PL, G, kColdOp>(cx, t); cold_store<NS, W, PL, G, kColdOp>(cx, cp); vcopy(cp, t);
+            cold_load<NS, W, PL, G, kColdOg>(cx, t); cold_store<NS, W, PL, G, kColdOg>(cx, cg); vcopy(cg, t);
             const bool tb = c_start; c_start = o_start; o_start = tb;
             c_right = right;
         }
-        cold_store<NS, W, PL, kColdAold>(cx, cp);   // momentum of the extended end before this doubling (nuts.py:332-338 operands)
+        cold_store<NS, W, PL, G, kColdAold>(cx, cp);   // momentum of the extended end before this doubling (nuts.py:332-338 operands)
         const bool aold_start = c_start;
 
         // subtree node under construction: momentum sum tps, weights; its right-end momentum is always the current cp,
         // its left-end momentum and proposal position are identified by their sources
         double tps[NS], eq[NS], ep[NS];
+        double q0r[NS], q1r[NS];   // G = 4 without kQStage (NS = 1, plan 1): q of the last quad's leaves 0 / 1
         double tw = 0.0, ta = 0.0;
-        int qsrc = -1;   // proposal position: -2 first leaf of the last pair (eq), -1 the current state (cq), j >= 1 stack level j
+        // proposal position: -2 first leaf of the last pair / third leaf of the last quad (eq), -1 the current state (cq),
+        // -3 / -4 (quads) the last quad's leaf 1 / 0, j >= 1 stack level j
+        int qsrc = -1;
+        auto prop_q = [&](double (&t)[NS]) {
+            if (qsrc == -1) vcopy(t, cq);
+            else if (qsrc == -2) vcopy(t, eq);
+            else if (G == 4 && qsrc < -2) {
+                if constexpr (PairLds<NS, W, PL, G>::kQStage > 0)
+                    vload_as<NS>((lds_double*)cx.lds + (PairLds<NS, W, PL, G>::kL1 + (qsrc == -3 ? PairLds<NS, W, PL, G>::DP : 0)), t);
+                else if (qsrc == -3) vcopy(t, q1r);
+                else vcopy(t, q0r);
+            } else level_load_q<NS, W, PL, G>(cx, qsrc, t);
+        };
         // The proposal's energy and log-density are not carried through the merges: for qsrc < 0 they sit on lane `elane`
         // of the last pair's (en_last, lp_last), for qsrc >= 1 in that level's scalars; they are fetched when the node is
         // parked or accepted. (The sum of w * min(1, e^{-dE}) could leave the merges the same way -- accumulated on lanes
@@ -1133,27 +1173,27 @@ __device__ inline void nuts_transition2(TeamT& tm, const Target& tgt, const doub
         if (D == 0) {
             double v[NS], kinp, lp, en, ev;
             leapfrog_partial<NS>(tm, tgt, var, eps, cq, cp, cg, v, kinp, lp);
-            red_put<NS, W, PL>(cx, 0, kinp); red_put<NS, W, PL>(cx, 1, lp);   // (DPP butterflies for the lone leaf and the trajectory-level
-            const double s0 = red_gather<NS, W, PL>(cx);                   //  test measured 1 % slower on depth-3 trees, equal on C3)
+            red_put<NS, W, PL, G>(cx, 0, kinp); red_put<NS, W, PL, G>(cx, 1, lp);   // (DPP butterflies for the lone leaf and the trajectory-level
+            const double s0 = red_gather<NS, W, PL, G>(cx);                   //  test measured 1 % slower on depth-3 trees, equal on C3)
             if (leaf_scalars(s0, 1, en, ev) == 1) {
                 tw = readlane_f64(ev, 15); ta = readlane_f64(ev, 14);
                 en_last = en; lp_last = s0;
                 vcopy(tps, cp);
             }
-        } else {
+        } else if (G == 2 || D == 1) {
             const int n_pairs = 1 << (D - 1);
             for (int k = 0; k < n_pairs; ++k) {
                 double v[NS], kinA, lpA, kinB, lpB;
                 leapfrog_partial<NS>(tm, tgt, var, eps, cq, cp, cg, v, kinA, lpA);
-                red_put<NS, W, PL>(cx, 0, kinA); red_put<NS, W, PL>(cx, 1, lpA);
+                red_put<NS, W, PL, G>(cx, 0, kinA); red_put<NS, W, PL, G>(cx, 1, lpA);
                 vcopy(eq, cq); vcopy(ep, cp);
                 leapfrog_partial<NS>(tm, tgt, var, eps, cq, cp, cg, v, kinB, lpB);   // speculative w.r.t. the first leaf's divergence test
-                red_put<NS, W, PL>(cx, 2, kinB); red_put<NS, W, PL>(cx, 3, lpB);
+                red_put<NS, W, PL, G>(cx, 2, kinB); red_put<NS, W, PL, G>(cx, 3, lpB);
 #pragma unroll
                 for (int s = 0; s < NS; ++s) tps[s] = ep[s] + cp[s];
-                red_put<NS, W, PL>(cx, 4, pdot_v<NS>(tps, var, ep));   // var (.) ep is the first leaf's velocity, re-formed (same rounded product)
-                red_put<NS, W, PL>(cx, 5, pdot<NS>(tps, v));
-                const double s0 = red_gather<NS, W, PL>(cx);
+                red_put<NS, W, PL, G>(cx, 4, pdot_v<NS>(tps, var, ep));   // var (.) ep is the first leaf's velocity, re-formed (same rounded product)
+                red_put<NS, W, PL, G>(cx, 5, pdot<NS>(tps, v));
+                const double s0 = red_gather<NS, W, PL, G>(cx);
                 // this pair closes m right children (levels 1..m)
                 const int m = __builtin_ctz(~static_cast<unsigned>(k) | (1u << (D - 1)));
                 double en, ev;
@@ -1171,13 +1211,14 @@ __device__ inline void nuts_transition2(TeamT& tm, const Target& tgt, const doub
                     tw = wsum; ta = aA + aB;
                     if (turn) { turning = true; break; }
                 }
+                if constexpr (G == 2) {   // (G = 4: the one pair of a depth-1 subtree, m = 0 and nothing to park)
                 // ---- cascade level 1 (left end of the in-flight pair node = ep)
                 if (m >= 1) {
                     double alp[NS], arp[NS], aps[NS];
                     double aw, aa;
-                    level1_load<NS, W, PL>(cx, alp, arp, aps);   // (requesting it before the leaf scalars measured -8 %: one more live address)
-                    level_scal_get_wa<NS, W, PL>(cx, 1, aw, aa);
-                    const double sj = cascade_dots<NS, W, PL>(cx, var, alp, arp, aps, ep, tps, v);
+                    level1_load<NS, W, PL, G>(cx, alp, arp, aps);   // (requesting it before the leaf scalars measured -8 %: one more live address)
+                    level_scal_get_wa<NS, W, PL, G>(cx, 1, aw, aa);
+                    const double sj = cascade_dots<NS, W, PL, G>(cx, var, alp, arp, aps, ep, tps, v);
                     const bool turn = red_any_nonpositive(sj, 0, 6);
                     const double wsum = aw + tw;
                     const bool take_b = uniform_true(team_uniform(tm, rng, win) * wsum < tw);
@@ -1188,11 +1229,11 @@ __device__ inline void nuts_transition2(TeamT& tm, const Target& tgt, const doub
                 // ---- cascade levels 2..m: node a = stack[j]; the in-flight node's left end is stack[j-1]'s
                 for (int j = 2; j <= m; ++j) {
                     double blp[NS], brp[NS], bps[NS], tl[NS];
-                    levelN_load<NS, W, PL>(cx, j, 0, blp); levelN_load<NS, W, PL>(cx, j, 1, brp); levelN_load<NS, W, PL>(cx, j, 2, bps);
-                    level_load_lp<NS, W, PL>(cx, j - 1, tl);
+                    levelN_load<NS, W, PL, G>(cx, j, 0, blp); levelN_load<NS, W, PL, G>(cx, j, 1, brp); levelN_load<NS, W, PL, G>(cx, j, 2, bps);
+                    level_load_lp<NS, W, PL, G>(cx, j - 1, tl);
                     double bw, ba;
-                    level_scal_get_wa<NS, W, PL>(cx, j, bw, ba);
-                    const double sj = cascade_dots<NS, W, PL>(cx, var, blp, brp, bps, tl, tps, v);
+                    level_scal_get_wa<NS, W, PL, G>(cx, j, bw, ba);
+                    const double sj = cascade_dots<NS, W, PL, G>(cx, var, blp, brp, bps, tl, tps, v);
                     const bool turn = red_any_nonpositive(sj, 0, 6);
                     const double wsum = bw + tw;
                     const bool take_b = uniform_true(team_uniform(tm, rng, win) * wsum < tw);
@@ -1203,10 +1244,10 @@ __device__ inline void nuts_transition2(TeamT& tm, const Target& tgt, const doub
                 if (turning) break;
                 if (k + 1 < n_pairs) {   // park the node at level m + 1 (the last pair's cascade result stays in flight)
                     double tl[NS], tqv[NS];
-                    if (m == 0) vcopy(tl, ep); else level_load_lp<NS, W, PL>(cx, m, tl);
+                    if (m == 0) vcopy(tl, ep); else level_load_lp<NS, W, PL, G>(cx, m, tl);
                     if (qsrc == -1) vcopy(tqv, cq);
                     else if (qsrc == -2) vcopy(tqv, eq);
-                    else level_load_q<NS, W, PL>(cx, qsrc, tqv);
+                    else level_load_q<NS, W, PL, G>(cx, qsrc, tqv);
 #ifndef LMC_PARK_REORDER_MIN_NS
 #define LMC_PARK_REORDER_MIN_NS 4
 #endif
@@ -1218,18 +1259,193 @@ __device__ inline void nuts_transition2(TeamT& tm, const Target& tgt, const doub
                     // the ISA, round 4). Measured, alternating runs on one box (profiles/r04_iteration_tail_ab.txt, box 3): C5
                     // +1 ... +2 %, C4 equal; C3 (two-element slices) -0.1 ... -0.4 %, hence the condition.
                     constexpr bool kParkReorder = NS >= LMC_PARK_REORDER_MIN_NS;
-                    if constexpr (kParkReorder) level_scal_park<NS, W, PL>(cx, m + 1, tw, ta, qsrc, elane, en_last, lp_last);
+                    if constexpr (kParkReorder) level_scal_park<NS, W, PL, G>(cx, m + 1, tw, ta, qsrc, elane, en_last, lp_last);
                     if (m == 0) {
-                        level1_store<NS, W, PL>(cx, tl, cp, tqv);
+                        level1_store<NS, W, PL, G>(cx, tl, cp, tqv);
                     } else {
                         if constexpr (kParkReorder) {
 #pragma unroll
                             for (int s = 0; s < NS; ++s) asm volatile("" : "+v"(tl[s]), "+v"(tqv[s]));
                         }
-                        levelN_store<NS, W, PL>(cx, m + 1, 0, tl); levelN_store<NS, W, PL>(cx, m + 1, 1, cp);
-                        levelN_store<NS, W, PL>(cx, m + 1, 2, tps); levelN_store<NS, W, PL>(cx, m + 1, 3, tqv);
+                        levelN_store<NS, W, PL, G>(cx, m + 1, 0, tl); levelN_store<NS, W, PL, G>(cx, m + 1, 1, cp);
+                        levelN_store<NS, W, PL, G>(cx, m + 1, 2, tps); levelN_store<NS, W, PL, G>(cx, m + 1, 3, tqv);
                     }
-                    if constexpr (!kParkReorder) level_scal_park<NS, W, PL>(cx, m + 1, tw, ta, qsrc, elane, en_last, lp_last);
+                    if constexpr (!kParkReorder) level_scal_park<NS, W, PL, G>(cx, m + 1, tw, ta, qsrc, elane, en_last, lp_last);
+                }
+                }   // G == 2
+            }
+        } else if constexpr (G == 4) {
+            // ---- leaf quads (depth >= 2). Leaves 1..3 are integrated before the divergence of the earlier ones is known;
+            // their decisions are then applied in the sequential algorithm's order, stopping at the first divergence or
+            // turn: A = leaves 0,1 (level-0 draw, span check), B = leaves 2,3 (same), A o B (level-1 draw, three U-turn
+            // checks, nuts.py:384-417), then the cascade from level 2 up. Only accepted leaves are counted.
+            using L = PairLds<NS, W, PL, G>;
+            lds_double* const qst = (lds_double*)cx.lds + L::kL1;   // q of leaves 0 / 1 (kQStage)
+            const int n_quads = 1 << (D - 2);
+            for (int k = 0; k < n_quads; ++k) {
+                static_assert(NS <= 2, "leaf quads: the left end of a depth-2 subtree waits in two rows of the reduction buffer");
+                double v[NS], kin, lpl, a0[NS], a1[NS];
+                leapfrog_partial<NS>(tm, tgt, var, eps, cq, cp, cg, v, kin, lpl);
+                red_put<NS, W, PL, G>(cx, 0, kin); red_put<NS, W, PL, G>(cx, 1, lpl);
+                if constexpr (L::kQStage > 0) vstore_as<NS>(qst, cq); else vcopy(q0r, cq);
+                vcopy(a0, cp);
+                leapfrog_partial<NS>(tm, tgt, var, eps, cq, cp, cg, v, kin, lpl);
+                red_put<NS, W, PL, G>(cx, 2, kin); red_put<NS, W, PL, G>(cx, 3, lpl);
+                if constexpr (L::kQStage > 0) vstore_as<NS>(qst + L::DP, cq); else vcopy(q1r, cq);
+                vcopy(a1, cp);
+                leapfrog_partial<NS>(tm, tgt, var, eps, cq, cp, cg, v, kin, lpl);
+                red_put<NS, W, PL, G>(cx, 4, kin); red_put<NS, W, PL, G>(cx, 5, lpl);
+                vcopy(eq, cq); vcopy(ep, cp);
+                leapfrog_partial<NS>(tm, tgt, var, eps, cq, cp, cg, v, kin, lpl);
+                red_put<NS, W, PL, G>(cx, 6, kin); red_put<NS, W, PL, G>(cx, 7, lpl);
+                const double s0 = red_gather<NS, W, PL, G>(cx);   // kinetic / log-density sums of leaf i on lanes 16i+7 / 16i+15
+                // the ten U-turn dots, each with the pair form's per-lane FMA order: level 0 of A and of B, then A o B
+                // (cascade_dots with node a = {a0, a1, a0 + a1}, in-flight node {left end ep, tps, right-end velocity v})
+                double ta01[NS], va1[NS];
+#pragma unroll
+                for (int s = 0; s < NS; ++s) { ta01[s] = a0[s] + a1[s]; va1[s] = var[s] * a1[s]; tps[s] = ep[s] + cp[s]; }
+                red_put<NS, W, PL, G>(cx, 0, pdot_v<NS>(ta01, var, a0));
+                red_put<NS, W, PL, G>(cx, 1, pdot<NS>(ta01, va1));   // leaf 1's velocity, re-formed (same rounded product)
+                red_put<NS, W, PL, G>(cx, 2, pdot_v<NS>(tps, var, ep));
+                red_put<NS, W, PL, G>(cx, 3, pdot<NS>(tps, v));
+                double s1, s2;
+                {
+                    double d0 = 0.0, d1 = 0.0, d2 = 0.0, d3 = 0.0, d4 = 0.0, d5 = 0.0;
+#pragma unroll
+                    for (int s = 0; s < NS; ++s) {   // cascade_dots, term for term
+                        const double p1 = ta01[s] + ep[s];
+                        const double p2 = a1[s] + tps[s];
+                        const double ps = ta01[s] + tps[s];
+                        const double valp = var[s] * a0[s], vtlp = var[s] * ep[s], varp = var[s] * a1[s];
+                        d0 = __builtin_fma(ps, valp, d0); d1 = __builtin_fma(ps, v[s], d1);
+                        d2 = __builtin_fma(p1, valp, d2); d3 = __builtin_fma(p1, vtlp, d3);
+                        d4 = __builtin_fma(p2, varp, d4); d5 = __builtin_fma(p2, v[s], d5);
+                        tps[s] = ps;
+                    }
+                    red_put<NS, W, PL, G>(cx, 4, d0); red_put<NS, W, PL, G>(cx, 5, d1);
+                    red_put<NS, W, PL, G>(cx, 6, d2); red_put<NS, W, PL, G>(cx, 7, d3);
+                    s1 = red_gather<NS, W, PL, G>(cx);   // level 0 of A (values 0, 1), of B (2, 3), A o B (4..7 ...
+                    red_put<NS, W, PL, G>(cx, 0, d4); red_put<NS, W, PL, G>(cx, 1, d5);
+                    s2 = red_gather<NS, W, PL, G>(cx);   // ... and 0, 1 here); DS operations run in issue order: no wait
+                }
+                // the U-turn checks as lane masks at once (red_any_nonpositive's ballot): the two sums leave the live set
+                const unsigned long long np1 = ballot64(s1 <= 0.0), np2 = ballot64(s2 <= 0.0);
+                // ---- leaf scalars of the four leaves (leaf_scalars on lanes 15 / 31 / 47 / 63)
+                const ExpLanesConst ec = exp_lanes_const();
+                const double en = 0.5 * dpp_f64<0x118>(s0) - s0;
+                double de_x = en - e0;
+                const unsigned long long rare = ballot64(!(fabs(de_x) < emax)) | ballot64((-de_x) - coff > 600.0);
+                de_x = isnan(de_x) ? __builtin_inf() : de_x;   // (a NaN leaf diverges: its weights are never used)
+                auto weights = [&]() {
+                    const double x = -de_x;
+                    const double xn = dpp_f64<0x101>(x);
+                    const double arg = odd_lane ? (x - coff) : ((xn - coff) + fmin(xn, 0.0));
+                    return exp_lanes<NS, W, PL, G>(cx, ec, arg);
+                };
+                double twA = 0.0, taA = 0.0;
+                // the sequential path of leaves i0, i0 + 1 (leaf_scalars' rare path); hold: A's weights, which the pair
+                // form has parked at level 1 by then, follow an offset move
+                auto leaves_seq = [&](int i0, bool hold) -> int {
+                    int seen = 0;
+                    for (int i = i0; i < i0 + 2; ++i) {
+                        const double dei = readlane_f64(de_x, 15 + 16 * i);
+                        ++n_leap; ++seen;
+                        if (!(fabs(dei) < emax)) { diverging = true; break; }
+                        const double xi = -dei;
+                        if (xi - coff > 600.0) {
+                            const double f = exp_uniform(coff - xi);
+                            const int lane = lane_id();
+                            if (lane >= 1 && lane < kLevelScalDoubles / 4) {
+                                lds_double* sc = (lds_double*)cx.lds + (L::kScal + 4 * lane);
+                                sc[0] = sc[0] * f; sc[1] = sc[1] * f;
+                            }
+                            if (hold) { twA = twA * f; taA = taA * f; }
+                            coff = xi;
+                        }
+                    }
+                    return seen;
+                };
+                const bool fast = (rare & ((1ull << 15) | (1ull << 31) | (1ull << 47) | (1ull << 63))) == 0ull;
+                auto mde_update = [&](double dx, bool examined) {
+                    const bool upd = (fabs(dx) > fabs(mde)) & examined;
+                    mde = upd ? dx : mde;
+                };
+                // ---- A: leaves 0, 1
+                int seen = 2;
+                if (fast) n_leap += 2; else seen = leaves_seq(0, false);
+                double ev = weights();
+                double w2 = readlane_f64(ev, 47), a2w = readlane_f64(ev, 46), w3 = readlane_f64(ev, 63), a3w = readlane_f64(ev, 62);
+                mde_update(de_x, lane15 | (lane31 & (seen == 2)));
+                if (diverging) break;
+                int elane_a;
+                {
+                    const double w0 = readlane_f64(ev, 15), a0w = readlane_f64(ev, 14);
+                    const double w1 = readlane_f64(ev, 31), a1w = readlane_f64(ev, 30);
+                    const bool turn = (np1 & ((1ull << 7) | (1ull << 15))) != 0ull;
+                    const double wsum = w0 + w1;
+                    const bool take_b = uniform_true(team_uniform(tm, rng, win) * wsum < w1);   // drawn even if turning
+                    elane_a = take_b ? 31 : 15;
+                    twA = wsum; taA = a0w + a1w;
+                    if (turn) { turning = true; break; }
+                }
+                // ---- B: leaves 2, 3 (their running max |dE| joins lanes 15 / 31 after leaves 0 / 1, as in the pair form)
+                if (fast) n_leap += 2;
+                else {
+                    seen = leaves_seq(2, true);
+                    ev = weights();
+                    w2 = readlane_f64(ev, 47); a2w = readlane_f64(ev, 46); w3 = readlane_f64(ev, 63); a3w = readlane_f64(ev, 62);
+                }
+                mde_update(upper_half_down(de_x), lane15 | (lane31 & (seen == 2)));
+                if (diverging) break;
+                {
+                    const bool turn = (np1 & ((1ull << 23) | (1ull << 31))) != 0ull;
+                    const double wsum = w2 + w3;
+                    const bool take_b = uniform_true(team_uniform(tm, rng, win) * wsum < w3);
+                    elane = take_b ? 63 : 47;
+                    tw = wsum; ta = a2w + a3w;
+                    if (turn) { turning = true; break; }
+                }
+                // ---- A o B (level 1)
+                {
+                    const bool turn = ((np1 & ((1ull << 39) | (1ull << 47) | (1ull << 55) | (1ull << 63))) |
+                                       (np2 & ((1ull << 7) | (1ull << 15)))) != 0ull;
+                    const double wsum = twA + tw;
+                    const bool take_b = uniform_true(team_uniform(tm, rng, win) * wsum < tw);
+                    if (!take_b) elane = elane_a;
+                    tw = wsum; ta = taA + ta;
+                    qsrc = elane == 63 ? -1 : elane == 47 ? -2 : elane == 31 ? -3 : -4;
+                    en_last = en; lp_last = s0;
+                    if (turn) { turning = true; break; }
+                }
+                // ---- cascade levels 2..m: node a = stack[j]; the in-flight node's left end is a0 (j = 2) or stack[j-1]'s
+                const int m = 1 + __builtin_ctz(~static_cast<unsigned>(k) | (1u << (D - 2)));
+                for (int j = 2; j <= m; ++j) {
+                    double blp[NS], brp[NS], bps[NS], tl[NS];
+                    levelN_load<NS, W, PL, G>(cx, j, 0, blp); levelN_load<NS, W, PL, G>(cx, j, 1, brp); levelN_load<NS, W, PL, G>(cx, j, 2, bps);
+                    if (j == 2) vcopy(tl, a0); else levelN_load<NS, W, PL, G>(cx, j - 1, 0, tl);
+                    double bw, ba;
+                    level_scal_get_wa<NS, W, PL, G>(cx, j, bw, ba);
+                    const double sj = cascade_dots<NS, W, PL, G>(cx, var, blp, brp, bps, tl, tps, v);
+                    const bool turn = red_any_nonpositive(sj, 0, 6);
+                    const double wsum = bw + tw;
+                    const bool take_b = uniform_true(team_uniform(tm, rng, win) * wsum < tw);
+                    if (!take_b) qsrc = j;
+                    tw = wsum; ta = ba + ta;
+                    if (turn) { turning = true; break; }
+                }
+                if (turning) break;
+                if (k + 1 < n_quads) {   // park the node at level m + 1 >= 2
+                    double tl[NS], tqv[NS];
+                    if (m == 1) vcopy(tl, a0); else levelN_load<NS, W, PL, G>(cx, m, 0, tl);
+                    prop_q(tqv);
+                    levelN_store<NS, W, PL, G>(cx, m + 1, 0, tl); levelN_store<NS, W, PL, G>(cx, m + 1, 1, cp);
+                    levelN_store<NS, W, PL, G>(cx, m + 1, 2, tps); levelN_store<NS, W, PL, G>(cx, m + 1, 3, tqv);
+                    level_scal_park<NS, W, PL, G>(cx, m + 1, tw, ta, qsrc, elane, en_last, lp_last);
+                } else if (D == 2) {
+                    // the subtree's left end for the trajectory-level test: rows 6 / 7 of the reduction buffer, which nothing
+                    // touches before that test reads it back
+#pragma unroll
+                    for (int s = 0; s < NS; ++s) ((lds_double*)cx.lds)[(6 + s) * 64 + lane_id()] = a0[s];
                 }
             }
         }
@@ -1246,15 +1462,13 @@ __device__ inline void nuts_transition2(TeamT& tm, const Target& tgt, const doub
         }
         if (uniform_true(team_uniform(tm, rng, win) * (w_start + wn) < tw)) {   // biased progressive
             double tqv[NS];
-            if (qsrc == -1) vcopy(tqv, cq);
-            else if (qsrc == -2) vcopy(tqv, eq);
-            else level_load_q<NS, W, PL>(cx, qsrc, tqv);
+            prop_q(tqv);
             vstore_as<NS>((glb_double*)qrow, tqv);
             if (qsrc < 0) {
                 prop_e = readlane_f64(en_last, elane); prop_logp = readlane_f64(lp_last, elane);
             } else {
                 double w_, a_;
-                level_scal_get<NS, W, PL>(cx, qsrc, w_, a_, prop_e, prop_logp);
+                level_scal_get<NS, W, PL, G>(cx, qsrc, w_, a_, prop_e, prop_logp);
                 prop_e = first_f64(prop_e); prop_logp = first_f64(prop_logp);
             }
         }
@@ -1262,14 +1476,18 @@ __device__ inline void nuts_transition2(TeamT& tm, const Target& tgt, const doub
         double tlp[NS], psum[NS], op[NS], aold[NS];
         if (D == 0) vcopy(tlp, cp);
         else if (D == 1) vcopy(tlp, ep);
-        else level_load_lp<NS, W, PL>(cx, D - 1, tlp);
-        cold_load<NS, W, PL, kColdPsum>(cx, psum); cold_load<NS, W, PL, kColdOp>(cx, op); cold_load<NS, W, PL, kColdAold>(cx, aold);
+        else if (G == 4 && D == 2) {
+#pragma unroll
+            for (int s = 0; s < NS; ++s) tlp[s] = ((const lds_double*)cx.lds)[(6 + s) * 64 + lane_id()];
+        }
+        else level_load_lp<NS, W, PL, G>(cx, D - 1, tlp);
+        cold_load<NS, W, PL, G, kColdPsum>(cx, psum); cold_load<NS, W, PL, G, kColdOp>(cx, op); cold_load<NS, W, PL, G, kColdAold>(cx, aold);
 #pragma unroll
         for (int s = 0; s < NS; ++s) {   // in place; float32 storage when the start momentum is float32
             const double t = psum[s] + tps[s];
             psum[s] = momentum_f32 ? static_cast<double>(static_cast<float>(t)) : t;
         }
-        cold_store<NS, W, PL, kColdPsum>(cx, psum);
+        cold_store<NS, W, PL, G, kColdPsum>(cx, psum);
         double ov[NS], av[NS];   // velocities of the untouched end and of the extended end as it was before this doubling
         end_velocity<NS>(ov, var, op, o_start);
         end_velocity<NS>(av, var, aold, aold_start);
@@ -1294,9 +1512,9 @@ __device__ inline void nuts_transition2(TeamT& tm, const Target& tgt, const doub
             }
         }
         c_start = false;
-        red_put<NS, W, PL>(cx, 0, d0); red_put<NS, W, PL>(cx, 1, d1); red_put<NS, W, PL>(cx, 2, d2);
-        red_put<NS, W, PL>(cx, 3, d3); red_put<NS, W, PL>(cx, 4, d4); red_put<NS, W, PL>(cx, 5, d5);
-        if (red_any_nonpositive(red_gather<NS, W, PL>(cx), 0, 6)) { turning = true; exhausted = false; break; }
+        red_put<NS, W, PL, G>(cx, 0, d0); red_put<NS, W, PL, G>(cx, 1, d1); red_put<NS, W, PL, G>(cx, 2, d2);
+        red_put<NS, W, PL, G>(cx, 3, d3); red_put<NS, W, PL, G>(cx, 4, d4); red_put<NS, W, PL, G>(cx, 5, d5);
+        if (red_any_nonpositive(red_gather<NS, W, PL, G>(cx), 0, 6)) { turning = true; exhausted = false; break; }
     }
 
     const double wn_end = first_f64(tot[0]), an_end = first_f64(tot[1]);
@@ -1581,14 +1799,16 @@ __device__ __forceinline__ void diag_mass_update(const CA& A, const PT& P, long 
 
 // RNG = 0: the reference's stream (numpy legacy MT19937 + polar method, same-seed parity); 1: momentum from Philox
 // (philox_normals: the throughput mode, its own kernel instantiation so that the parity kernels are untouched by it)
-// PL: the LDS plan (PairLds<NS, W, PL>). 0 keeps the MT19937 state and three cold slots in LDS -- best for shallow trees, where the
+// PL: the LDS plan (PairLds<NS, W, PL, G>). 0 keeps the MT19937 state and three cold slots in LDS -- best for shallow trees, where the
 // momentum draw is a fifth of an iteration; 1 (one-wave kernels) uses the generator in place and keeps stack level 2 in LDS
 // instead -- best for deep trees, where every other pair cascades through it. The plans differ in WHERE a chain's private data
 // lives, never in arithmetic: results are bit-identical (tests/test_gpu_round5.py::test_lds_plans_are_bit_identical), so the
 // engine is free to pick per launch from the tree sizes the chains report (A.tree_hint; lmc_engine.hip: choose_lds_plan).
 // (Both plans as two bodies of ONE kernel with every chain choosing for itself were built first and lose 7-20 % under
 // either plan -- profiles/r05_lds_plan_dual_body_ab.txt -- the kernel per plan keeps each plan's code as it was measured.)
-template <int NS, int W, template <int> class TargetT, int RNG = 0, int PL = 0>
+// G: the leaf-group width of the NUTS tree build (nuts_transition2); the default is the form the engine runs, 2 pins the pair form
+// (A/B runs, the bit-identity test).
+template <int NS, int W, template <int> class TargetT, int RNG = 0, int PL = 0, int G = run_leaf_group(NS, W)>
 __global__ __launch_bounds__(64 * W, run_waves_per_simd(NS, W)) void run_kernel(ChainArrays, SamplerParams, const double* tparams) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const long long t_resident = wall_clock64();   // constant-rate clock: the chain's residence time (kCtWaveTicks)
@@ -1654,18 +1874,18 @@ __global__ __launch_bounds__(64 * W, run_waves_per_simd(NS, W)) void run_kernel(
     long long ct_maxdepth = 0, ct_divs = 0, ct_after = 0, ct_leap = 0;
     int status = 0;
 
-    // compile-time LDS plan (PairLds<NS, W, PL>), the chain's scratch row for what does not fit
+    // compile-time LDS plan (PairLds<NS, W, PL, G>), the chain's scratch row for what does not fit
     static_assert(NS <= 4, "sampling kernels hold at most four elements per lane");
     PairCtx cx;
     cx.lds = lds;
     cx.glb = A0.scratch + static_cast<long long>(c) * A0.scratch_stride;
     cx.nlds = P0.nlds;
     cx.wave = tm.wave();
-    cx.wave_red = W > 1 ? cx.wave * PairLds<NS, W>::kRedWave : 0;
+    cx.wave_red = W > 1 ? cx.wave * PairLds<NS, W, PL, G>::kRedWave : 0;
     cx.wave_scal = W > 1 ? cx.wave * kLevelScalDoubles : 0;
-    cx.red_lane = static_cast<int>(reinterpret_cast<size_t>((lds_double*)lds + (red_lane_init() + cx.wave_red)));
+    cx.red_lane = static_cast<int>(reinterpret_cast<size_t>((lds_double*)lds + (red_lane_init(PairLds<NS, W, PL, G>::kRedRows) + cx.wave_red)));
     cx.xpar = 0;
-    if (tid < kExpTableDoubles) lds[PairLds<NS, W>::kExp + tid] = kExp2Table[2 * tid];
+    if (tid < kExpTableDoubles) lds[PairLds<NS, W, PL, G>::kExp + tid] = kExp2Table[2 * tid];
     tm.sync();
 
 #ifdef LMC_PHASE_TIMING   // diagnostic build (tools/phase_timing.py): s_memtime ticks per phase replace three counters
@@ -1736,7 +1956,7 @@ __global__ __launch_bounds__(64 * W, run_waves_per_simd(NS, W)) void run_kernel(
         TransitionOut out;
         if (P.kind == 0) {
             const int md = (tune && iter_count < 200) ? P.early_max_treedepth : P.max_treedepth;
-            nuts_transition2<NS, PL>(tm, tgt, vard, rng, cx, qrow, q, p0, g0, e0, logp0, step_size, P.emax, md,
+            nuts_transition2<NS, PL, G>(tm, tgt, vard, rng, cx, qrow, q, p0, g0, e0, logp0, step_size, P.emax, md,
                                  momentum_f32, out);
             vload<NS>(qrow, q);   // the proposal was written to the chain's row of A.q
             // (handing it over in registers when the last doubling accepted it measured -4 % on depth-3 trees)

@@ -87,6 +87,13 @@ __device__ __forceinline__ double swap32_add(double a, double b) {   // [a_lo + 
     return __hiloint2double(static_cast<int>(hi[0]), static_cast<int>(lo[0])) +
            __hiloint2double(static_cast<int>(hi[1]), static_cast<int>(lo[1]));
 }
+__device__ __forceinline__ double upper_half_down(double x) {   // lanes 0-31 <- lanes 32-63 (the upper half keeps its own)
+    const auto lo = __builtin_amdgcn_permlane32_swap(static_cast<unsigned>(__double2loint(x)),
+                                                     static_cast<unsigned>(__double2loint(x)), false, false);
+    const auto hi = __builtin_amdgcn_permlane32_swap(static_cast<unsigned>(__double2hiint(x)),
+                                                     static_cast<unsigned>(__double2hiint(x)), false, false);
+    return __hiloint2double(static_cast<int>(hi[1]), static_cast<int>(lo[1]));
+}
 __device__ __forceinline__ double swap16_add(double a, double b) {   // rows [a0+a1, b0+b1, a2+a3, b2+b3]
     const auto lo = __builtin_amdgcn_permlane16_swap(static_cast<unsigned>(__double2loint(a)),
                                                      static_cast<unsigned>(__double2loint(b)), false, false);

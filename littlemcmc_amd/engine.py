@@ -167,6 +167,7 @@ _TUNING_ENV = {
     "LMC_DENSE_CACHE_ROWS": ("dense_cache_rows_p1", lambda v: int(v) + 1),
     "LMC_DENSE_LDS_SLOTS": ("dense_lds_slots_p1", lambda v: int(v) + 1),
     "LMC_CHOL_HBM": ("chol_hbm", lambda v: int(int(v) != 0)),
+    "LMC_LEAF_GROUP": ("leaf_group", int),
 }
 
 
@@ -445,6 +446,10 @@ class Engine:
     def last_run_plan(self):
         """LDS plan of the most recent run() launch: "shallow" / "deep" (None: nothing launched, or a kernel with one plan)."""
         return {_abi.LDS_PLAN_SHALLOW: "shallow", _abi.LDS_PLAN_DEEP: "deep"}.get(int(self._lib.lmc_engine_last_run_plan(self._h)))
+
+    def last_run_leaf_group(self):
+        """Leaf-group width of the tree build of the most recent run() launch: 2 (pairs) / 4 (quads); None: nothing launched."""
+        return int(self._lib.lmc_engine_last_run_leaf_group(self._h)) or None
 
     def run_streams(self):
         """Raw HIP stream handles run() launches its kernels on (one per sub-block of chains)."""

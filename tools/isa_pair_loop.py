@@ -2,7 +2,12 @@
 """What a leapfrog of the NUTS pair loop costs in issued instructions, by PURPOSE (static census of the loop's own basic blocks).
 
     hipcc ... -gline-tables-only -S --cuda-device-only -o /tmp/isa/eng_g.s littlemcmc_amd/csrc/lmc_engine.hip
-    python tools/isa_pair_loop.py /tmp/isa/eng_g.s _ZN3lmc10run_kernelILi4ELi1ENS_12FunnelTargetELi0ELi1EEE
+    python tools/isa_pair_loop.py /tmp/isa/eng_g.s _ZN3lmc10run_kernelILi4ELi1ENS_12FunnelTargetELi0ELi1ELi2EEE
+    python tools/isa_pair_loop.py /tmp/isa/eng_g.s _ZN3lmc10run_kernelILi2ELi1ENS_9AR1TargetELi0ELi1ELi4EEE   (leaf quads)
+
+A kernel whose last template argument (the leaf-group width G of run_kernel) is 4 builds its subtrees of depth >= 2 from leaf
+QUADS: the tool then recovers the QUAD loop instead (anchored on the quad's momentum sums) and reports per leapfrog with
+a quad = 4; every scratch instruction inside the recovered loop is listed (there should be none).
 
 The compiler's own loop annotation is of no use here (the pair loop of nuts_transition2 is not a natural loop after
 structurisation: its blocks are labelled with the depth of the iteration loop), so the loop is recovered from the control-flow
@@ -127,6 +132,8 @@ def main():
     asm, kernel = sys.argv[1], sys.argv[2]
     src = open(os.path.join(CSRC, "lmc_sampler.hpp")).read().split("\n")
     line_of = lambda needle: next(i for i, l in enumerate(src, 1) if needle in l)  # noqa: E731
+    if re.search(r"Li4EEEv", kernel) or kernel.rstrip("E").endswith("Li4"):
+        return main_quads(asm, kernel, line_of)
     L_second = line_of("for (int s = 0; s < NS; ++s) tps[s] = ep[s] + cp[s];")   # (arithmetic of the pair body itself: inlined calls carry the callee's lines)
     L_depth = line_of("++depth;   // nuts.py:315")
     L_pairs = line_of("for (int k = 0; k < n_pairs; ++k)")
@@ -246,6 +253,91 @@ def main():
         grand += per
         print("%-86s %6.3f %6d %6d %5d %5d %5d %5d | %6.1f" % (name, w, c["valu"], c["salu"], c["lds"], c["vmem"], c["smem"], c["wait"], per))
     print("%-86s %6s %6s %6s %5s %5s %5s %5s | %6.1f" % ("TOTAL (weighted)", "", "", "", "", "", "", "", grand))
+
+
+def main_quads(asm, kernel, line_of):
+    """The quad loop of nuts_transition2<.., G = 4>: body (four leapfrogs, three gathers, the four leaves' scalars, the
+    merges of A, B and A o B) once per quad, cascade levels >= 2 and the park every second quad, the sequential path ~0."""
+    L_depth = line_of("++depth;   // nuts.py:315")
+    L_anchor = line_of("ta01[s] = a0[s] + a1[s];")
+    L_quads = line_of("const int n_quads")
+    L_scal = line_of("---- leaf scalars of the four leaves")
+    L_rare0 = line_of("auto leaves_seq = [&]")
+    L_rare1 = line_of("return seen;")
+    L_merge = line_of("---- A: leaves 0, 1")
+    L_casc = line_of("---- cascade levels 2..m: node a = stack[j]; the in-flight node's left end is a0")
+    L_park = line_of("if (k + 1 < n_quads) {   // park")
+    blocks, order = parse(asm, kernel)
+    succ = edges(blocks, order)
+    has = lambda b, line: any(loc == ("lmc_sampler.hpp", line) for _o, _t, loc in blocks[b])  # noqa: E731
+    banned = {b for b in order if has(b, L_depth)}
+    starts = [b for b in order if has(b, L_anchor)]
+    if not starts:
+        raise SystemExit("no block carries line %d (the quad's momentum sums)" % L_anchor)
+    loop = set()
+    for s_ in starts:
+        loop |= scc_of(s_, succ, banned)
+
+    def region_of_line(ln):
+        if L_rare0 <= ln <= L_rare1:
+            return "rare", 0.0
+        if L_quads <= ln < L_scal:
+            return "integrate + gathers", 1.0
+        if L_scal <= ln < L_merge:
+            return "leaf scalars", 1.0
+        if L_merge <= ln < L_casc:
+            return "merges A, B, A o B", 1.0
+        if L_casc <= ln < L_park:
+            return "cascade levels >= 2", 0.5   # every second quad closes level 2, sum over j >= 2 of 2^-(j-1)
+        if L_park <= ln < L_depth:
+            return "park", 0.5                  # every second quad's node stays on the stack
+        return None
+
+    region, last = {}, ("integrate + gathers", 1.0)
+    for b in order:
+        if b not in loop:
+            continue
+        own = [region_of_line(loc[1]) for _o, _t, loc in blocks[b] if loc and loc[0] == "lmc_sampler.hpp"]
+        own = [r for r in own if r is not None]
+        if own:
+            last = min(own, key=lambda r: r[1])
+        region[b] = last
+    ranges = {fn: function_ranges(os.path.join(CSRC, fn)) for fn in os.listdir(CSRC) if fn.endswith(".hpp")}
+
+    def func_of(loc):
+        name = "?"
+        for first, nm in ranges.get(loc[0], []) if loc else []:
+            if first <= loc[1]:
+                name = nm
+        return name
+
+    tot = collections.defaultdict(collections.Counter)
+    scratch = []
+    for b in order:
+        if b not in loop:
+            continue
+        for op, t, loc in blocks[b]:
+            fn = func_of(loc)
+            key = region[b]
+            if fn in ("mt_twist", "mt_regen"):
+                key = ("uniforms: MT19937 regeneration (once per 624 words)", 2.0 / 624.0)
+            elif fn in ("exp_uniform", "exp_uniform_fast"):
+                key = ("rare", 0.0)
+            tot[key][kind_of(op)] += 1
+            if op.startswith("scratch_"):
+                scratch.append((b, loc, t))
+    print("kernel %s" % kernel)
+    print("quad loop: %d basic blocks of %d, %d instructions (static)" % (len(loop), len(order), sum(sum(c.values()) for c in tot.values())))
+    print("%-52s %6s %6s %6s %5s %5s %5s %5s | %s" % ("region", "weight", "valu", "salu", "lds", "vmem", "smem", "wait", "weighted, per LEAPFROG (a quad = 4)"))
+    grand = 0.0
+    for (name, w), c in sorted(tot.items(), key=lambda kv: -sum(kv[1].values()) * kv[0][1]):
+        per = 0.25 * w * sum(c.values())
+        grand += per
+        print("%-52s %6.3f %6d %6d %5d %5d %5d %5d | %6.1f" % (name, w, c["valu"], c["salu"], c["lds"], c["vmem"], c["smem"], c["wait"], per))
+    print("%-52s %6s %6s %6s %5s %5s %5s %5s | %6.1f" % ("TOTAL (weighted)", "", "", "", "", "", "", "", grand))
+    print("scratch instructions in the quad loop: %d" % len(scratch))
+    for b, loc, t in scratch:
+        print("  %s %s %s" % (b, loc, t))
 
 
 if __name__ == "__main__":
