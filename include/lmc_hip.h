@@ -330,6 +330,11 @@ int32_t lmc_engine_last_run_plan(lmc_engine* e);
 /* The leaf-group width of the NUTS tree build the most recent lmc_engine_run() launch ran (2 = leaf pairs, 4 = leaf quads;
  * lmc_tuning.leaf_group); 0 before the first launch and for kernels that do not build trees in groups. */
 int32_t lmc_engine_last_run_leaf_group(lmc_engine* e);
+/* The dense kernel the most recent lmc_engine_run() launched: 1 = one chain per wavefront with its own matrix sweep
+ * (run_dense_kernel), 2 = eight chains per workgroup around the shared matrix in LDS (run_dense_coop_kernel,
+ * LMC_POT_FULL up to model_ndim 128, lmc_tuning.dense_coop_off switches it off); 0 before the first launch and for
+ * engines without a dense matrix or on the general kernels. */
+int32_t lmc_engine_last_run_dense_kernel(lmc_engine* e);
 
 /* ---- results (synchronise the stream). dst shapes: trace [chains][n_iters][dim]; stats [chains][n_iters] */
 int lmc_engine_get_trace(lmc_engine* e, double* dst, int64_t iter_begin, int64_t n_iters);

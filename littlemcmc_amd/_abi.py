@@ -137,6 +137,7 @@ _SIGNATURES = {
     "lmc_engine_run_streams": (C.c_int, [_P, _P, C.c_int32]),
     "lmc_engine_last_run_plan": (C.c_int32, [_P]),
     "lmc_engine_last_run_leaf_group": (C.c_int32, [_P]),
+    "lmc_engine_last_run_dense_kernel": (C.c_int32, [_P]),
     "lmc_engine_copy_window_async": (C.c_int, [_P, C.POINTER(WindowDst), C.c_int64, C.c_int64]),
     "lmc_engine_copy_wait": (C.c_int, [_P]),
     "lmc_host_alloc": (_P, [C.c_uint64]),

@@ -314,6 +314,7 @@ struct lmc_engine {
     int plan_now = 0;                                 // the plan of the launches being enqueued (lds_plan == 2: follows the tree-size hint with hysteresis)
     int plan_last = -1;                               // the plan the most recent lmc_engine_run() actually launched with (-1: nothing launched yet)
     int leaf_group = 2;                               // NUTS tree build of the sampling kernel (lmc_sampler.hpp: run_kernel<.., G>): 2 pairs, 4 quads
+    int dense_kernel_last = 0;                        // dense kernel of the most recent lmc_engine_run(): 1 per chain (run_dense_kernel), 2 shared matrix (run_dense_coop_kernel), 0 none
     bool wide = false;          // the general kernels (lmc_wide.hpp): one chain = 16 wavefronts, dpad = 1024 * ns -- model_ndim > 1024,
                                 // dense matrices beyond 256 dimensions, float64 adaptive diagonals
     double* init_diag64 = nullptr;   // [C][dpad] wide: the initial diagonal in float64
@@ -637,6 +638,7 @@ static int dense_run(lmc_engine* e, SamplerParams P) {
         e->D.cache_rows = 0;
         e->D.lds_slots = slots < 0 ? 0 : slots;
     }
+    e->dense_kernel_last = coop ? 2 : 1;
     const long long end = P.iter_begin + P.n_iters;
     if (n_sub > 1) e->sub_pending = true;
     long long it = P.iter_begin;
@@ -1222,6 +1224,10 @@ int32_t lmc_engine_run_lds_bytes(lmc_engine* e) {
 int32_t lmc_engine_last_run_leaf_group(lmc_engine* e) {
     if (!e || e->plan_last < 0 || e->cfg.kind != LMC_KIND_NUTS || e->wide || e->cfg.potential >= LMC_POT_FULL || e->cfg.target_family == LMC_TARGET_EXTERNAL) return 0;
     return e->leaf_group;
+}
+int32_t lmc_engine_last_run_dense_kernel(lmc_engine* e) {
+    if (!e || e->wide || e->cfg.potential < LMC_POT_FULL) return 0;
+    return e->dense_kernel_last;
 }
 int32_t lmc_engine_last_run_plan(lmc_engine* e) {
     if (!e || e->plan_last < 0 || e->wide || e->cfg.potential >= LMC_POT_FULL || e->cfg.target_family == LMC_TARGET_EXTERNAL) return 0;
@@ -1878,6 +1884,7 @@ int lmc_engine_reset_tuning(lmc_engine* e) {
     if (e->stop_host) __atomic_store_n(e->stop_host + 24, 0, __ATOMIC_RELEASE);   // tree-size hint: nothing reported yet
     if (e->lds_plan == 2) e->plan_now = 0;
     e->plan_last = -1;
+    e->dense_kernel_last = 0;
     // QuadPotentialDiag.reset() is a no-op (quadpotential.py:138-140): only the adaptive potential resets
     int rc = launch_reset(e, 1, e->cfg.potential == LMC_POT_DIAG_ADAPT ? 1 : 0);
     if (rc != LMC_OK) return rc;

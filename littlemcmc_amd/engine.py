@@ -451,6 +451,12 @@ class Engine:
         """Leaf-group width of the tree build of the most recent run() launch: 2 (pairs) / 4 (quads); None: nothing launched."""
         return int(self._lib.lmc_engine_last_run_leaf_group(self._h)) or None
 
+    def last_run_dense_kernel(self):
+        """Dense kernel of the most recent run() launch: "per_chain" (run_dense_kernel, one chain per wavefront) / "shared"
+        (run_dense_coop_kernel, eight chains per workgroup around the matrix in LDS); None: nothing launched, no dense
+        matrix, or the general kernels."""
+        return {1: "per_chain", 2: "shared"}.get(int(self._lib.lmc_engine_last_run_dense_kernel(self._h)))
+
     def run_streams(self):
         """Raw HIP stream handles run() launches its kernels on (one per sub-block of chains)."""
         arr = (C.c_void_p * _abi.MAX_RUN_STREAMS)()

@@ -101,6 +101,25 @@ def test_built_in_targets_and_the_run_time_user_family():
     assert [lib.lmc_has_target(i) for i in range(8)] == [1, 1, 1, 1, 1, 1, 1, 0]
 
 
+def test_last_run_dense_kernel_names_the_library_codes():
+    """lmc_engine_last_run_dense_kernel: 0 (nothing / not dense) -> None, 1 -> "per_chain", 2 -> "shared"."""
+    assert _abi.load().lmc_engine_last_run_dense_kernel(None) == 0
+
+    class Lib:
+        code = 0
+
+        def lmc_engine_last_run_dense_kernel(self, h):
+            return self.code
+
+    eng = object.__new__(lmc.Engine)
+    eng._lib, eng._h = Lib(), None
+    got = []
+    for code in (0, 1, 2, 3):
+        eng._lib.code = code
+        got.append(eng.last_run_dense_kernel())
+    assert got == [None, "per_chain", "shared", None]
+
+
 def test_user_target_compiles_with_hiprtc_without_a_gpu():
     """The run-time compiler needs no device: the functor-dependent kernels of an engine shape (three, and the sampling kernel's second LDS plan) come out of
     hiprtc as a gfx950 code object with the lowered names the engine looks up; the result is cached by content."""

@@ -19,7 +19,7 @@ import littlemcmc_amd as lmc
 from littlemcmc_amd import _abi
 from oracle import lmc_oracle as orc
 from oracle import targets as otargets
-from tests._gpu_util import INT_STATS, device_target
+from tests._gpu_util import INT_STATS, dense_snapshots, device_target, replay_dense
 
 pytestmark = pytest.mark.gpu
 
@@ -191,32 +191,7 @@ def _oracle_and_device_steps(g):
     return ostep, dstep, start
 
 
-def _snapshots(ostep, start, seed, tune, draws):
-    rng = np.random.RandomState(int(seed))
-    q = np.array(start, dtype="d")
-    ostep.tune = bool(tune)
-    ostep.reset_tuning()
-    snaps, outs = [], []
-    for i in range(tune + draws):
-        if i == 0:
-            ostep.iter_count = 0
-        if i == tune:
-            ostep.tune = False
-        pot, ad = ostep.pot, ostep.adapt
-        snap = dict(q=q.copy(), rng=rng.get_state(), tune=ostep.tune, iter_count=ostep.iter_count,
-                    log_step=float(np.ravel(ad.log_step)[0]), log_bar=float(np.ravel(ad.log_bar)[0]),
-                    hbar=float(np.ravel(ad.hbar)[0]), da_count=ad.count, n_samples=pot.n_samples)
-        if isinstance(pot, orc.FullAdaptPotential):
-            snap.update(cov=pot.cov.copy(), chol=pot.chol.copy(), fore_mean=pot.fore.mean.copy(),
-                        fore_raw_cov=pot.fore.raw.copy(), fore_n=pot.fore.n_samples, back_mean=pot.back.mean.copy(),
-                        back_raw_cov=pot.back.raw.copy(), back_n=pot.back.n_samples, window=pot.window,
-                        previous_update=pot.previous_update)
-        q, st = ostep.astep(q, rng)
-        m = ostep.last_margins
-        snaps.append(snap)
-        outs.append(dict(q=q.copy(), stats={k: np.ravel(v)[0] for k, v in st.items()},
-                         margin=min(m.lb, m.turn, m.div), rng_pos=rng.get_state()[2]))
-    return snaps, outs
+_snapshots = dense_snapshots
 
 
 @pytest.mark.parametrize("name", DENSE_E2E)
@@ -327,49 +302,8 @@ def test_dense_adaptation_learns_the_target_covariance():
 # ---------------------------------------------------------------------------------------------------
 def _replay(ostep, dstep, start, seed, tune, draws, f32_born, label):
     snaps, outs = _snapshots(ostep, start, seed, tune, draws)
-    tol = REPLAY_F32 if f32_born else REPLAY_F64
-    floor = DECISION if f32_born else 1e-9
-    checked = 0
-    for tune_flag in (True, False):
-        idx = [i for i, s in enumerate(snaps) if s["tune"] == tune_flag]
-        if not idx:
-            continue
-        eng = dstep._make_engine(len(idx))
-        try:
-            eng.set_position(np.stack([snaps[i]["q"] for i in idx]))
-            for c, i in enumerate(idx):
-                eng.set_rng_state(c, snaps[i]["rng"])
-            eng.set_chain_state({k: np.stack([np.asarray(snaps[i][k]) for i in idx]) for k in
-                                 ("log_step", "log_bar", "hbar", "da_count", "iter_count", "n_samples")})
-            if "cov" in snaps[idx[0]]:
-                eng.set_dense_state({k: np.stack([np.asarray(snaps[i][k]) for i in idx]) for k in
-                                     ("cov", "chol", "fore_mean", "fore_raw_cov", "fore_n", "back_mean", "back_raw_cov",
-                                      "back_n", "window", "previous_update")})
-            eng.reserve(1, keep_trace=True)
-            eng.run(1 if tune_flag else 0, 0, 1)
-            assert not eng.status().any()
-            q = eng.trace()[:, 0]
-            stats = {k: v[:, 0] for k, v in dstep._stats_from_engine(eng, 0, 1).items()}
-            dense_after = eng.get_dense_state(fields=("cov",)) if "cov" in snaps[idx[0]] else None
-            for c, i in enumerate(idx):
-                want, tag = outs[i], "%s iter %d" % (label, i)
-                if want["margin"] < floor:
-                    continue
-                for sname, val in want["stats"].items():
-                    got = stats[sname][c]
-                    if sname in INT_STATS:
-                        assert got == val, (tag, sname, got, val, want["margin"])
-                    else:
-                        assert np.isclose(got, val, rtol=tol, atol=tol * (1 + abs(want["stats"].get("energy", 0.0)))), (
-                            tag, sname, got, val)
-                np.testing.assert_allclose(q[c], want["q"], rtol=tol, atol=tol * (1 + np.abs(want["q"]).max()), err_msg=tag)
-                if dense_after is not None and i + 1 < len(snaps) and snaps[i + 1]["tune"] == tune_flag:
-                    cs = np.abs(snaps[i + 1]["cov"]).max()
-                    np.testing.assert_allclose(dense_after["cov"][c], snaps[i + 1]["cov"], rtol=0, atol=2 * tol * cs, err_msg=tag)
-                checked += 1
-        finally:
-            eng.close()
-    return checked
+    return replay_dense(dstep, snaps, outs, REPLAY_F32 if f32_born else REPLAY_F64, DECISION if f32_born else 1e-9,
+                        label)["checked"]
 
 
 @pytest.mark.parametrize("d,family", [(100, "ar1"), (130, "std_normal"), (200, "ar1"), (256, "std_normal")])
