@@ -8,123 +8,64 @@
 #include "lmc_dense.hpp"
 #include "lmc_tick.hpp"
 #include "lmc_dense_launch.hpp"
-#ifdef LMC_USER_TARGET_HEADER
-#include LMC_USER_TARGET_HEADER
-#endif
+#include "lmc_dispatch.hpp"
 
 namespace lmc {
 
-#ifdef LMC_USER_TARGET_HEADER
-#define DENSE_USER_CASE(CALL) case LMC_TARGET_USER: { CALL(UserTarget); } break;
-#else
-#define DENSE_USER_CASE(CALL)
-#endif
-
-#if defined(LMC_USER_TARGET_HEADER) && defined(LMC_ONLY_USER)
-#define DENSE_FAMILY_SWITCH(family, CALL) \
-    switch (family) {                     \
-        DENSE_USER_CASE(CALL)             \
-        default: return kDenseUnsupported; \
-    }
-#else
-#define DENSE_FAMILY_SWITCH(family, CALL)                                   \
-    switch (family) {                                                       \
-        case LMC_TARGET_STD_NORMAL: { CALL(StdNormalTarget); } break;       \
-        case LMC_TARGET_DIAG_GAUSSIAN: { CALL(DiagGaussianTarget); } break; \
-        case LMC_TARGET_AR1: { CALL(AR1Target); } break;                    \
-        case LMC_TARGET_FUNNEL: { CALL(FunnelTarget); } break;              \
-        case LMC_TARGET_NORMAL1D: { CALL(Normal1DTarget); } break;          \
-        DENSE_USER_CASE(CALL)                                               \
-        default: return kDenseUnsupported;                                  \
-    }
-#endif
-
-#define DENSE_SHAPE_SWITCH(ns, mat_f64, BODY)                                              \
-    if (mat_f64) {                                                                         \
-        typedef double MatT;                                                               \
-        switch (ns) {                                                                      \
-            case 1: { constexpr int NS = 1; BODY; } break;                                 \
-            case 2: { constexpr int NS = 2; BODY; } break;                                 \
-            case 4: { constexpr int NS = 4; BODY; } break;                                 \
-            default: return kDenseUnsupported;                                             \
-        }                                                                                  \
-    } else {                                                                               \
-        typedef float MatT;                                                                \
-        switch (ns) {                                                                      \
-            case 1: { constexpr int NS = 1; BODY; } break;                                 \
-            case 2: { constexpr int NS = 2; BODY; } break;                                 \
-            case 4: { constexpr int NS = 4; BODY; } break;                                 \
-            default: return kDenseUnsupported;                                             \
-        }                                                                                  \
-    }
+template <class MatT>
+struct MatTag { typedef MatT type; };
+// (elements per lane, matrix element type): f(NS, MatTag<MatT>{}) for the shape, nullptr for any other
+template <class F>
+static auto with_dense_shape(int ns, bool mat_f64, F&& f) {
+    return with_int<1, 2, 4>(ns, [&](auto NS) { return mat_f64 ? f(NS, MatTag<double>{}) : f(NS, MatTag<float>{}); });
+}
+template <template <int> class T>
+static auto run_dense_for(TargetTag<T>, int ns, bool mat_f64) {
+    return with_dense_shape(ns, mat_f64, [](auto NS, auto M) { return &run_dense_kernel<NS, typename decltype(M)::type, T>; });
+}
+template <template <int> class T>
+static auto trajectory_dense_for(TargetTag<T>, int ns, bool mat_f64) {
+    return with_dense_shape(ns, mat_f64, [](auto NS, auto M) { return &dense_trajectory_kernel<NS, typename decltype(M)::type, T>; });
+}
 
 int dense_launch_run(int family, int ns, bool mat_f64, hipStream_t stream, const ChainArrays& A, const DenseArrays& D,
                      const SamplerParams& P, const double* tparams, int n_chains) {
-    const dim3 grid(n_chains > 0 ? n_chains : A.chains), block(64);
     const int lds = dense_lds_doubles(A.dpad) * 8 + D.cache_rows * A.dpad * (mat_f64 ? 8 : 4) + D.lds_slots * A.dpad * 8;
-    (void)hipGetLastError();
-#define RUN_CALL(T) \
-    DENSE_SHAPE_SWITCH(ns, mat_f64, {                                                                               \
-        if (lds > 64 * 1024) {                                                                                      \
-            hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(&run_dense_kernel<NS, MatT, T>),     \
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, lds);                  \
-            if (err != hipSuccess) return static_cast<int>(err);                                                    \
-        }                                                                                                           \
-        hipLaunchKernelGGL((run_dense_kernel<NS, MatT, T>), grid, block, lds, stream, A, D, P, tparams);            \
-    })
-    DENSE_FAMILY_SWITCH(family, RUN_CALL)
-#undef RUN_CALL
-    return static_cast<int>(hipGetLastError());
+    const auto kernel = with_target(family, [&](auto t) { return run_dense_for(t, ns, mat_f64); });
+    return launch(kernel, dim3(n_chains > 0 ? n_chains : A.chains), dim3(64), lds, stream, A, D, P, tparams);
 }
 
 int dense_launch_trajectory(int family, int ns, bool mat_f64, hipStream_t stream, const ChainArrays& A,
                             const DenseArrays& D, const double* tparams, const double* q0, const double* p0,
                             int p0_is_f32, int sdot_mode, double eps, int n_fwd, int n_back, double* oq, double* op,
                             double* ov, double* og, double* oe, double* ol) {
-    const dim3 grid(A.chains), block(64);
-    const int lds = 2 * A.dpad * 8;
-    (void)hipGetLastError();
-#define TRAJ_CALL(T)                                                                                                   \
-    DENSE_SHAPE_SWITCH(ns, mat_f64, hipLaunchKernelGGL((dense_trajectory_kernel<NS, MatT, T>), grid, block, lds, stream, A, D, \
-                                                       tparams, q0, p0, p0_is_f32, sdot_mode, eps, n_fwd, n_back, oq, op, ov,  \
-                                                       og, oe, ol))
-    DENSE_FAMILY_SWITCH(family, TRAJ_CALL)
-#undef TRAJ_CALL
-    return static_cast<int>(hipGetLastError());
+    const auto kernel = with_target(family, [&](auto t) { return trajectory_dense_for(t, ns, mat_f64); });
+    return launch(kernel, dim3(A.chains), dim3(64), 2 * A.dpad * 8, stream, A, D, tparams, q0, p0, p0_is_f32, sdot_mode, eps, n_fwd,
+                  n_back, oq, op, ov, og, oe, ol);
 }
 
 int dense_launch_momentum(int ns, hipStream_t stream, const ChainArrays& A, const DenseArrays& D, double* out) {
-    const dim3 grid(A.chains), block(64);
-    const int lds = 2 * A.dpad * 8;
-    (void)hipGetLastError();
-    switch (ns) {
-        case 1: hipLaunchKernelGGL((dense_momentum_kernel<1>), grid, block, lds, stream, A, D, out); break;
-        case 2: hipLaunchKernelGGL((dense_momentum_kernel<2>), grid, block, lds, stream, A, D, out); break;
-        case 4: hipLaunchKernelGGL((dense_momentum_kernel<4>), grid, block, lds, stream, A, D, out); break;
-        default: return kDenseUnsupported;
-    }
-    return static_cast<int>(hipGetLastError());
+    const auto kernel = with_int<1, 2, 4>(ns, [](auto NS) { return &dense_momentum_kernel<NS>; });
+    return launch(kernel, dim3(A.chains), dim3(64), 2 * A.dpad * 8, stream, A, D, out);
 }
 
 int dense_launch_adapt(hipStream_t stream, const ChainArrays& A, const DenseArrays& D, double multiplier,
                        int update_window, int* mask, int chain_begin, int n_chains, int expect_iter) {
     const int lds = dense_adapt_lds_bytes(A.d, A.dpad);
     const dim3 grid(n_chains > 0 ? n_chains : A.chains);
-    (void)hipGetLastError();
     // lmc_config.tuning.chol_hbm (a test knob): the factorisation through HBM at every size an engine allocated the work area for,
     // so that the FullAdapt goldens of the small shapes check it against the register form (same factor bit for bit)
     const bool force_hbm = D.force_chol_hbm != 0 && D.chol_work != nullptr;
     if (D.mat_f64)   // QuadPotentialFullAdapt(dtype="float64"): covariance, factor and factorisation in float64 (general kernels)
-        hipLaunchKernelGGL((dense_adapt_kernel<0, double>), grid, dim3(kCholHbmThreads), lds, stream, A, D, multiplier, update_window, mask, chain_begin, expect_iter);
-    else if (dense_adapt_grid(A.d) == 8 && !force_hbm)
-        hipLaunchKernelGGL(dense_adapt_kernel<8>, grid, dim3(64), lds, stream, A, D, multiplier, update_window, mask, chain_begin, expect_iter);
-    else if (dense_adapt_grid(A.d) == 16 && !force_hbm)
-        hipLaunchKernelGGL(dense_adapt_kernel<16>, grid, dim3(256), lds, stream, A, D, multiplier, update_window, mask, chain_begin, expect_iter);
-    else if (dense_adapt_grid(A.d) == 32 && !force_hbm)
-        hipLaunchKernelGGL(dense_adapt_kernel<32>, grid, dim3(1024), lds, stream, A, D, multiplier, update_window, mask, chain_begin, expect_iter);
-    else   // the factorisation through HBM: d > 256 (or the test knob)
-        hipLaunchKernelGGL(dense_adapt_kernel<0>, grid, dim3(kCholHbmThreads), lds, stream, A, D, multiplier, update_window, mask, chain_begin, expect_iter);
-    return static_cast<int>(hipGetLastError());
+        return launch(dense_adapt_kernel<0, double>, grid, dim3(kCholHbmThreads), lds, stream, A, D, multiplier, update_window, mask, chain_begin, expect_iter);
+    if (dense_adapt_grid(A.d) == 8 && !force_hbm)
+        return launch(dense_adapt_kernel<8>, grid, dim3(64), lds, stream, A, D, multiplier, update_window, mask, chain_begin, expect_iter);
+    if (dense_adapt_grid(A.d) == 16 && !force_hbm)
+        return launch(dense_adapt_kernel<16>, grid, dim3(256), lds, stream, A, D, multiplier, update_window, mask, chain_begin, expect_iter);
+    if (dense_adapt_grid(A.d) == 32 && !force_hbm)
+        return launch(dense_adapt_kernel<32>, grid, dim3(1024), lds, stream, A, D, multiplier, update_window, mask, chain_begin, expect_iter);
+    // the factorisation through HBM: d > 256 (or the test knob)
+    return launch(dense_adapt_kernel<0>, grid, dim3(kCholHbmThreads), lds, stream, A, D, multiplier, update_window, mask, chain_begin, expect_iter);
 }
 
 // ---- the tick state machine (lmc_tick.hpp: tick_step) with a dense mass matrix: densities evaluated by the caller
@@ -175,26 +116,19 @@ __global__ __launch_bounds__(64, dense_waves_per_simd(NS)) void tick_dense_kerne
 
 int tick_dense_launch(int ns, bool mat_f64, hipStream_t stream, const ChainArrays& A, const DenseArrays& D,
                       const TickArrays& K, const SamplerParams& P, const double* logp, const double* grad, int* adapt_mask) {
-    const dim3 grid(A.chains), block(64);
-    const int lds = 2 * A.dpad * 8;
-    (void)hipGetLastError();
-    DENSE_SHAPE_SWITCH(ns, mat_f64, hipLaunchKernelGGL((tick_dense_kernel<NS, MatT>), grid, block, lds, stream, A, D, K, P, logp,
-                                                       grad, adapt_mask))
-    return static_cast<int>(hipGetLastError());
+    const auto kernel = with_dense_shape(ns, mat_f64, [](auto NS, auto M) { return &tick_dense_kernel<NS, typename decltype(M)::type>; });
+    return launch(kernel, dim3(A.chains), dim3(64), 2 * A.dpad * 8, stream, A, D, K, P, logp, grad, adapt_mask);
 }
 
 int dense_launch_reset(hipStream_t stream, const ChainArrays& A, const DenseArrays& D, const void* cov1T,
                        const void* fac1, const double* raw1T, const double* mean1, double weight, int window, int d8) {
     const int per_chain = (d8 * A.dpad + 255) / 256;
-    (void)hipGetLastError();
     const dim3 grid(A.chains, per_chain < 64 ? per_chain : 64);
     if (D.mat_f64)
-        hipLaunchKernelGGL(dense_reset_kernel<double>, grid, dim3(256), 0, stream, A, D, static_cast<const double*>(cov1T),
-                           static_cast<const double*>(fac1), raw1T, mean1, weight, window, d8);
-    else
-        hipLaunchKernelGGL(dense_reset_kernel<float>, grid, dim3(256), 0, stream, A, D, static_cast<const float*>(cov1T),
-                           static_cast<const float*>(fac1), raw1T, mean1, weight, window, d8);
-    return static_cast<int>(hipGetLastError());
+        return launch(dense_reset_kernel<double>, grid, dim3(256), 0, stream, A, D, static_cast<const double*>(cov1T),
+                      static_cast<const double*>(fac1), raw1T, mean1, weight, window, d8);
+    return launch(dense_reset_kernel<float>, grid, dim3(256), 0, stream, A, D, static_cast<const float*>(cov1T),
+                  static_cast<const float*>(fac1), raw1T, mean1, weight, window, d8);
 }
 
 }  // namespace lmc

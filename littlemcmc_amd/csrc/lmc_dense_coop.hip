@@ -10,6 +10,7 @@
 #include "../../include/lmc_hip.h"
 #include "lmc_dense.hpp"
 #include "lmc_dense_launch.hpp"
+#include "lmc_dispatch.hpp"
 
 namespace lmc {
 
@@ -19,39 +20,29 @@ int dense_coop_lds_slots(int d, int dpad, int max_slots) {   // tree slots per c
     return static_cast<int>(slots < 0 ? 0 : slots);
 }
 
+typedef void (*CoopKernel)(ChainArrays, DenseArrays, SamplerParams, const double*, int);
+// the shared-matrix kernel of (family, ns), nullptr where there is none: the built-in families but the 1-D one (whatever the
+// build), one or two elements per lane (dpad <= 128: the float32 matrix fits one CU's LDS next to the panels)
+template <template <int> class T>
+static CoopKernel coop_kernel_for(TargetTag<T>, int ns) {
+    return with_int<1, 2>(ns, [](auto NS) -> CoopKernel {
+        if constexpr (std::is_same<TargetTag<T>, TargetTag<Normal1DTarget>>::value) return nullptr;
+        else return &run_dense_coop_kernel<NS, T>;
+    });
+}
+static CoopKernel coop_kernel(int family, int ns) {
+    return with_builtin_target(family, [&](auto t) { return coop_kernel_for(t, ns); });
+}
+
 int dense_coop_supported(int family, int ns, int d, int dpad) {
-    if (ns != 1 && ns != 2) return 0;                       // dpad <= 128: the float32 matrix fits one CU's LDS next to the panels
-    if (coop_lds_bytes(d, dpad, 0) > 160 * 1024) return 0;
-    switch (family) {
-        case LMC_TARGET_STD_NORMAL: case LMC_TARGET_DIAG_GAUSSIAN: case LMC_TARGET_AR1: case LMC_TARGET_FUNNEL: return 1;
-        default: return 0;
-    }
+    return coop_kernel(family, ns) != nullptr && coop_lds_bytes(d, dpad, 0) <= 160 * 1024;
 }
 
 int dense_launch_run_coop(int family, int ns, hipStream_t stream, const ChainArrays& A, const DenseArrays& D,
                           const SamplerParams& P, const double* tparams, int n_chains) {
     const int n = n_chains > 0 ? n_chains : A.chains;
-    const dim3 grid((n + kCoopWaves - 1) / kCoopWaves), block(64 * kCoopWaves);
-    const int lds = coop_lds_bytes(A.d, A.dpad, D.lds_slots);
-    (void)hipGetLastError();
-#define COOP_ONE(NSV, T)                                                                                             \
-    {                                                                                                                \
-        hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(&run_dense_coop_kernel<NSV, T>),          \
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, lds);                       \
-        if (err != hipSuccess) return static_cast<int>(err);                                                         \
-        hipLaunchKernelGGL((run_dense_coop_kernel<NSV, T>), grid, block, lds, stream, A, D, P, tparams, n);          \
-    }
-#define COOP_CALL(T) { if (ns == 1) COOP_ONE(1, T) else COOP_ONE(2, T) }
-    switch (family) {
-        case LMC_TARGET_STD_NORMAL: COOP_CALL(StdNormalTarget) break;
-        case LMC_TARGET_DIAG_GAUSSIAN: COOP_CALL(DiagGaussianTarget) break;
-        case LMC_TARGET_AR1: COOP_CALL(AR1Target) break;
-        case LMC_TARGET_FUNNEL: COOP_CALL(FunnelTarget) break;
-        default: return kDenseUnsupported;
-    }
-#undef COOP_CALL
-#undef COOP_ONE
-    return static_cast<int>(hipGetLastError());
+    return launch(coop_kernel(family, ns), dim3((n + kCoopWaves - 1) / kCoopWaves), dim3(64 * kCoopWaves),
+                  coop_lds_bytes(A.d, A.dpad, D.lds_slots), stream, A, D, P, tparams, n);
 }
 
 }  // namespace lmc

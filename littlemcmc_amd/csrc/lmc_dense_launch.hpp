@@ -1,13 +1,11 @@
 // Host-callable launchers of the dense-mass kernels (lmc_dense.hip); called by the C ABI in lmc_engine.hip.
-// Return value: 0 = launched, kDenseUnsupported = no such instantiation in this build, otherwise a hipError_t.
+// Return value: that of launch() (lmc_dispatch.hpp).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "lmc_dense_types.hpp"
 
 namespace lmc {
-
-constexpr int kDenseUnsupported = -1;
 
 // run / adapt: chains [P.chain_begin, P.chain_begin + n_chains) resp. [chain_begin, chain_begin + n_chains); n_chains <= 0 = all
 int dense_launch_run(int family, int ns, bool mat_f64, hipStream_t stream, const ChainArrays& A, const DenseArrays& D,

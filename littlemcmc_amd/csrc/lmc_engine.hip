@@ -19,19 +19,9 @@
 #include "lmc_dense_launch.hpp"
 #include "lmc_tick_launch.hpp"
 #include "lmc_wide_launch.hpp"
-#ifdef LMC_USER_TARGET_HEADER
-#include LMC_USER_TARGET_HEADER
-#endif
+#include "lmc_dispatch.hpp"
 
 using namespace lmc;
-
-// hipMemcpy(..., hipMemcpyDefault) on pageable host pointers can leave a stale "last error" behind (pointer-attribute
-// probing); clear it before a launch so that the hipGetLastError() after the launch reports THIS launch only.
-#define LMC_LAUNCH(...)            \
-    do {                           \
-        (void)hipGetLastError();   \
-        hipLaunchKernelGGL(__VA_ARGS__); \
-    } while (0)
 
 // ---------------------------------------------------------------------------------------------
 // unit kernels (share the device functions with run_kernel)
@@ -457,51 +447,6 @@ static void dev_free(lmc_engine* e, void* p) {
     (void)hipFree(p);
 }
 
-// ---- (family, NS) dispatch --------------------------------------------------------------------------
-#define LMC_NS_SWITCH(e, ns, BODY)                                      \
-    switch (ns) {                                                       \
-        case 1: { constexpr int NS = 1; BODY; } break;                  \
-        case 2: { constexpr int NS = 2; BODY; } break;                  \
-        case 4: { constexpr int NS = 4; BODY; } break;                  \
-        case 8: { constexpr int NS = 8; BODY; } break;                  \
-        case 16: { constexpr int NS = 16; BODY; } break;                \
-        default: return fail(e, LMC_ERR_INVALID, "unsupported vector width ns=%d", ns); \
-    }
-
-// M(NS, W, T) for every sampling-kernel shape of this build (LMC_PAIR_SHAPES, lmc_sampler.hpp)
-#ifdef LMC_EXPERIMENTAL_SHAPES
-#define LMC_FOR_EACH_SHAPE(M, T) M(1, 1, T) M(2, 1, T) M(4, 1, T) M(4, 2, T) M(4, 4, T) M(2, 8, T) M(2, 2, T) M(1, 4, T)
-#else
-#define LMC_FOR_EACH_SHAPE(M, T) M(1, 1, T) M(2, 1, T) M(4, 1, T) M(4, 2, T) M(4, 4, T)
-#endif
-
-#ifdef LMC_USER_TARGET_HEADER
-#define LMC_USER_CASE(KERNEL_CALL) \
-    case LMC_TARGET_USER: { KERNEL_CALL(UserTarget); } break;
-#else
-#define LMC_USER_CASE(KERNEL_CALL)
-#endif
-
-#if defined(LMC_USER_TARGET_HEADER) && defined(LMC_ONLY_USER)
-// JIT build around a user density: instantiate the kernels for that family only (seconds, not a minute)
-#define LMC_FAMILY_SWITCH(e, family, KERNEL_CALL)                                       \
-    switch (family) {                                                                   \
-        LMC_USER_CASE(KERNEL_CALL)                                                      \
-        default: return fail(e, LMC_ERR_INVALID, "target family %d is not in this build", family); \
-    }
-#else
-#define LMC_FAMILY_SWITCH(e, family, KERNEL_CALL)                                       \
-    switch (family) {                                                                   \
-        case LMC_TARGET_STD_NORMAL: { KERNEL_CALL(StdNormalTarget); } break;            \
-        case LMC_TARGET_DIAG_GAUSSIAN: { KERNEL_CALL(DiagGaussianTarget); } break;      \
-        case LMC_TARGET_AR1: { KERNEL_CALL(AR1Target); } break;                         \
-        case LMC_TARGET_FUNNEL: { KERNEL_CALL(FunnelTarget); } break;                   \
-        case LMC_TARGET_NORMAL1D: { KERNEL_CALL(Normal1DTarget); } break;               \
-        LMC_USER_CASE(KERNEL_CALL)                                                      \
-        default: return fail(e, LMC_ERR_INVALID, "unknown target family %d", family);   \
-    }
-#endif
-
 template <class T>
 struct DevBuf {   // RAII staging buffer: device copy of a host-or-device array
     T* p = nullptr;
@@ -511,10 +456,17 @@ struct DevBuf {   // RAII staging buffer: device copy of a host-or-device array
 
 // ---- dense mass matrices: host side -----------------------------------------------------------------------
 static int dense_fail(lmc_engine* e, int rc, const char* what) {
-    if (rc == kDenseUnsupported)
+    if (rc == kLaunchUnsupported)
         return fail(e, LMC_ERR_INVALID, "%s: no dense-mass kernel for target family %d / dim %d in this build", what,
                     e->cfg.target_family, e->cfg.dim);
     return fail(e, LMC_ERR_HIP, "%s: %s", what, hipGetErrorString(static_cast<hipError_t>(rc)));
+}
+
+// a launch() of the engine's own kernels as an LMC_* code (the family was checked at create: what a build can lack is the width)
+static int launched(lmc_engine* e, int rc) {
+    if (rc == 0) return LMC_OK;
+    if (rc == kLaunchUnsupported) return fail(e, LMC_ERR_INVALID, "unsupported vector width ns=%d", e->ns);
+    return fail(e, LMC_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(static_cast<hipError_t>(rc)));
 }
 
 // In-place lower Cholesky, column by column with the operation order of the device kernel (cholesky_registers in lmc_dense.hpp):
@@ -557,11 +509,8 @@ static int relay_mask_for(long long n) {
     return m - 1;
 }
 
-#ifdef LMC_USER_TARGET_HEADER
-static const bool kUserCompiledIn = true;
-#else
-static const bool kUserCompiledIn = false;
-#endif
+// a density compiled at run time (hiprtc): its kernels are a module's (user_launch), not this library's
+static bool rtc_user(int family) { return family == LMC_TARGET_USER && !kUserCompiledIn; }
 // dynamic LDS of a sampling-kernel workgroup under plan 0 (stack + tail: MT19937, team exchange) / plan 1 (stack only)
 static int sampling_lds_bytes(const lmc_engine* e, int plan = 0) {
     return plan == 1 ? e->lds_bytes1 : e->lds_bytes + lds_tail_doubles(e->run_w) * 8;
@@ -587,11 +536,6 @@ static int choose_lds_plan(lmc_engine* e, long long iter_begin) {
 
 static bool pot_f64(int potential) { return potential == LMC_POT_FULL_INV || potential == LMC_POT_FULL_F64; }
 
-#ifdef LMC_USER_TARGET_HEADER
-static const bool kUserCompiledInDense = true;   // a private library around a user density: its dense kernels are the per-wave ones
-#else
-static const bool kUserCompiledInDense = false;
-#endif
 static int dense_run(lmc_engine* e, SamplerParams P) {
     P.momentum_f32 = !pot_f64(e->cfg.potential);   // quadpotential.py:452 (float32) vs :413 / dtype="float64" (float64)
     P.adapt_mass = 0;
@@ -628,7 +572,8 @@ static int dense_run(lmc_engine* e, SamplerParams P) {
     // chain of launches of its own -- with FullAdapt two per tuning iteration -- and the tail of one is covered by the other
     const int n_sub = e->n_sub;
     HIP_TRY(e, order_sub_blocks_after_main(e));
-    bool coop = e->cfg.potential == LMC_POT_FULL && !kUserCompiledInDense &&
+    // (a private library around a user density runs its dense kernels in the per-wave form)
+    bool coop = e->cfg.potential == LMC_POT_FULL && !kUserCompiledIn &&
                 dense_coop_supported(e->cfg.target_family, e->ns, e->cfg.dim, e->dpad) != 0;
     if (e->cfg.tuning.dense_coop_off) coop = false;
     if (coop) {   // the LDS the panels and private regions leave holds the leading tree slots of the eight chains
@@ -673,6 +618,44 @@ static int dense_run(lmc_engine* e, SamplerParams P) {
     return LMC_OK;
 }
 
+// ---- the kernel a sampling launch runs --------------------------------------------------------------------------------
+typedef void (*RunKernel)(ChainArrays, SamplerParams, const double*);
+
+// The counter-based momentum stream (Philox), the deep-tree LDS plan (plan 1, one-wave shapes) and leaf pairs pinned where
+// quads are the default (run_leaf_group) are instantiations of their own. The LDS sizes lmc_engine_create computes are those
+// of the kernel chosen here (same plan, same leaf group).
+template <int NS, int W, template <int> class T>
+static RunKernel run_kernel_of_shape(const lmc_engine* e, int plan) {
+    if (e->cfg.rng_mode == LMC_RNG_PHILOX) return &run_kernel<NS, W, T, 1>;
+    if constexpr (W == 1) {
+        const bool pinned_pairs = e->leaf_group != run_leaf_group(NS, 1);
+        if (plan == 1) return pinned_pairs ? &run_kernel<NS, 1, T, 0, 1, 2> : &run_kernel<NS, 1, T, 0, 1>;
+        if (pinned_pairs) return &run_kernel<NS, 1, T, 0, 0, 2>;
+    }
+    return &run_kernel<NS, W, T>;
+}
+template <template <int> class T>
+static RunKernel run_kernel_for(TargetTag<T>, const lmc_engine* e, int plan) {
+#define X(NSV, WV) if (e->run_ns == NSV && e->run_w == WV) return run_kernel_of_shape<NSV, WV, T>(e, plan);
+    LMC_PAIR_SHAPES(X)
+#undef X
+    return nullptr;
+}
+// nullptr: no sampling kernel of shape (run_ns, run_w) in this build
+static RunKernel sampling_kernel(const lmc_engine* e, int plan) {
+    return with_target(e->cfg.target_family, [&](auto t) { return run_kernel_for(t, e, plan); });
+}
+
+// the unit kernels over the target family (lmc_unit_kernels.hpp)
+template <template <int> class T>
+static auto trajectory_kernel_for(TargetTag<T>, int ns) {
+    return with_int<1, 2, 4, 8, 16>(ns, [](auto NS) { return &trajectory_kernel<NS, T>; });
+}
+template <template <int> class T>
+static auto logp_kernel_for(TargetTag<T>, int ns) {
+    return with_int<1, 2, 4, 8, 16>(ns, [](auto NS) { return &logp_kernel<NS, T>; });
+}
+
 static int ns_for_dim(int d) {
     const int need = (d + 63) / 64;
     int ns = 1;
@@ -698,10 +681,8 @@ int32_t lmc_device_count(void) {
 }
 
 int32_t lmc_has_target(int32_t family) {
-#if !(defined(LMC_USER_TARGET_HEADER) && defined(LMC_ONLY_USER))
-    if (family >= LMC_TARGET_STD_NORMAL && family <= LMC_TARGET_NORMAL1D) return 1;
-#endif
-    if (family == LMC_TARGET_USER) return 1;       // compiled in (LMC_USER_TARGET_HEADER build) or loaded at run time
+    if (with_target(family, [](auto) { return true; })) return 1;   // its kernels are in this build
+    if (family == LMC_TARGET_USER) return 1;       // loaded at run time
     if (family == LMC_TARGET_EXTERNAL) return 1;   // no device functor: the host evaluates the density between ticks
     return 0;
 }
@@ -746,11 +727,9 @@ static int launch_reset(lmc_engine* e, int reset_step, int reset_mass) {
     const int blocks = static_cast<int>((n + threads - 1) / threads);
     const double log_step0 = std::log(e->initial_step);         // step_sizes.py:51
     const double mu = std::log(10 * e->initial_step);           // step_sizes.py:55
-    LMC_LAUNCH(reset_kernel, dim3(blocks), dim3(threads), 0, main_stream(e), e->A, e->init_mean, e->init_diag,
-                       e->init_diag64, e->cfg.mass_f64, e->init_weight, e->cfg.potential == LMC_POT_DIAG_ADAPT ? 1 : 0, log_step0, mu, reset_step,
-                       reset_mass, e->cfg.adaptation_window);
-    HIP_TRY(e, hipGetLastError());
-    return LMC_OK;
+    return launched(e, launch(reset_kernel, dim3(blocks), dim3(threads), 0, main_stream(e), e->A, e->init_mean, e->init_diag,
+                              e->init_diag64, e->cfg.mass_f64, e->init_weight, e->cfg.potential == LMC_POT_DIAG_ADAPT ? 1 : 0, log_step0, mu,
+                              reset_step, reset_mass, e->cfg.adaptation_window));
 }
 
 int lmc_engine_create(const lmc_config* cfg, lmc_engine** out) {
@@ -773,7 +752,7 @@ int lmc_engine_create(const lmc_config* cfg, lmc_engine** out) {
                                               "(float64 fixed matrices: LMC_POT_FULL_F64 / LMC_POT_FULL_INV)");
     // Shapes the fused kernels are not instantiated for run in the general kernels (lmc_wide.hpp: one chain = 16 wavefronts)
     // (... and a density compiled at run time meets a dense mass matrix there: hiprtc instantiates the general kernel for it)
-    const bool rtc_dense = cfg->target_family == LMC_TARGET_USER && !kUserCompiledInDense && cfg->potential >= LMC_POT_FULL &&
+    const bool rtc_dense = rtc_user(cfg->target_family) && cfg->potential >= LMC_POT_FULL &&
                            cfg->potential != LMC_POT_FULL_ADAPT;
     // cfg.tuning.force_general (a test knob like tuning.run_ns / run_w): every shape the general kernels can run takes them, so
     // that the goldens of the small shapes replay through them too
@@ -905,7 +884,7 @@ int lmc_engine_create(const lmc_config* cfg, lmc_engine** out) {
     e->leaf_group = (!wide && run_leaf_group(e->run_ns, e->run_w) == 4 && cfg->tuning.leaf_group != 2) ? 4 : 2;
     // kernels only, and the counter-based momentum stream its own default instantiation (the LDS sizes below must be those of
     // the kernel that runs)
-    if ((cfg->target_family == LMC_TARGET_USER && !kUserCompiledIn) || cfg->rng_mode == LMC_RNG_PHILOX)
+    if (rtc_user(cfg->target_family) || cfg->rng_mode == LMC_RNG_PHILOX)
         e->leaf_group = run_leaf_group(e->run_ns, e->run_w);
     const int lg = e->leaf_group;
     if (wide) {
@@ -943,7 +922,7 @@ int lmc_engine_create(const lmc_config* cfg, lmc_engine** out) {
             if (e->nlds1 <= e->nlds) e->lds_plan = 0;   // nothing gained: the plan would only move the generator out
             if (cfg->rng_mode == LMC_RNG_PHILOX) e->lds_plan = 0;   // (instantiated on the parity stream)
             e->lds_plan_wanted = e->lds_plan;
-            if (cfg->target_family == LMC_TARGET_USER && !kUserCompiledIn)
+            if (rtc_user(cfg->target_family))
                 e->lds_plan = 0;                         // until lmc_engine_load_user_run_plan1() hands the plan-1 kernel over
             e->plan_now = e->lds_plan == 1 ? 1 : 0;
         }
@@ -1174,43 +1153,17 @@ int lmc_engine_occupancy(lmc_engine* e, int32_t* resident_chains, int32_t* waves
     const int run_lds = sampling_lds_bytes(e);
     const int block = 64 * e->run_w;
     int per_cu = 0;
-    if (e->cfg.target_family == LMC_TARGET_USER && !kUserCompiledIn) {
+    if (rtc_user(e->cfg.target_family)) {
         if (!e->user_run) return fail(e, LMC_ERR_STATE, "the user density's kernels are not loaded");
         HIP_TRY(e, hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, e->user_run, block, static_cast<size_t>(run_lds)));
         *resident_chains = per_cu * cus;
         return LMC_OK;
     }
     // (the very instantiation run() launches: the counter-based momentum stream is its own kernel with its own registers)
-#define OCC_ONE(NSV, WV, T)                                                                                    \
-    if (!found && e->run_ns == NSV && e->run_w == WV) {                                                        \
-        found = true;                                                                                          \
-        if (e->cfg.rng_mode == LMC_RNG_PHILOX) {                                                               \
-            if (run_lds > 64 * 1024)                                                                           \
-                HIP_TRY(e, hipFuncSetAttribute(reinterpret_cast<const void*>(&run_kernel<NSV, WV, T, 1>),      \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, run_lds));          \
-            HIP_TRY(e, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, run_kernel<NSV, WV, T, 1>, block, \
-                                                                    static_cast<size_t>(run_lds)));            \
-        } else if (e->leaf_group != run_leaf_group(NSV, WV)) {                                                 \
-            HIP_TRY(e, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, run_kernel<NSV, WV, T, 0, 0, 2>,  \
-                                                                    block, static_cast<size_t>(run_lds)));     \
-        } else {                                                                                               \
-            if (run_lds > 64 * 1024)                                                                           \
-                HIP_TRY(e, hipFuncSetAttribute(reinterpret_cast<const void*>(&run_kernel<NSV, WV, T>),         \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, run_lds));          \
-            HIP_TRY(e, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, run_kernel<NSV, WV, T>, block,    \
-                                                                    static_cast<size_t>(run_lds)));            \
-        }                                                                                                      \
-    }
-    // every shape of LMC_PAIR_SHAPES (lmc_sampler.hpp), the experimental ones of a variant build included
-#define OCC_CALL(T)                                                                                            \
-    {                                                                                                          \
-        bool found = false;                                                                                    \
-        LMC_FOR_EACH_SHAPE(OCC_ONE, T)                                                                         \
-        if (!found) return fail(e, LMC_ERR_INVALID, "unsupported kernel shape ns=%d w=%d", e->run_ns, e->run_w); \
-    }
-    LMC_FAMILY_SWITCH(e, e->cfg.target_family, OCC_CALL)
-#undef OCC_CALL
-#undef OCC_ONE
+    const RunKernel kernel = sampling_kernel(e, 0);
+    if (!kernel) return fail(e, LMC_ERR_INVALID, "unsupported kernel shape ns=%d w=%d", e->run_ns, e->run_w);
+    HIP_TRY(e, allow_lds(kernel, run_lds));
+    HIP_TRY(e, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, block, static_cast<size_t>(run_lds)));
     *resident_chains = per_cu * cus;
     return LMC_OK;
 }
@@ -1244,7 +1197,7 @@ int lmc_engine_load_user_kernels(lmc_engine* e, const void* code_object, const c
     if (e->user_module) { (void)hipModuleUnload(e->user_module); e->user_module = nullptr; }
     e->user_run = e->user_trajectory = e->user_logp = nullptr;
     e->user_run1 = nullptr;
-    if (e->cfg.target_family == LMC_TARGET_USER && !kUserCompiledIn) { e->lds_plan = 0; e->plan_now = 0; }   // plan 0 until the plan-1 kernel is handed over
+    if (rtc_user(e->cfg.target_family)) { e->lds_plan = 0; e->plan_now = 0; }   // plan 0 until the plan-1 kernel is handed over
     HIP_TRY(e, hipModuleLoadData(&e->user_module, code_object));
     HIP_TRY(e, hipModuleGetFunction(&e->user_run, e->user_module, run_name));
     HIP_TRY(e, hipModuleGetFunction(&e->user_trajectory, e->user_module, trajectory_name));
@@ -1310,9 +1263,8 @@ int lmc_engine_diag_update(lmc_engine* e, int32_t tune) {
         return LMC_OK;
     }
     const dim3 grid(e->cfg.chains), block(64);
-    LMC_NS_SWITCH(e, e->ns, LMC_LAUNCH((mass_update_kernel<NS>), grid, block, 0, main_stream(e), e->A, P))
-    HIP_TRY(e, hipGetLastError());
-    return LMC_OK;
+    const auto kernel = with_int<1, 2, 4, 8, 16>(e->ns, [](auto NS) { return &mass_update_kernel<NS>; });
+    return launched(e, launch(kernel, grid, block, 0, main_stream(e), e->A, P));
 }
 
 int lmc_engine_set_step_jitter(lmc_engine* e, int32_t enable, double lo, double hi) {
@@ -1803,8 +1755,7 @@ int lmc_engine_seed(lmc_engine* e, const uint32_t* seeds) {
     HIP_TRY(e, hipMalloc(reinterpret_cast<void**>(&dseeds), e->cfg.chains * sizeof(uint32_t)));
     hipError_t err = hipMemcpyAsync(dseeds, seeds, e->cfg.chains * sizeof(uint32_t), hipMemcpyDefault, main_stream(e));
     if (err == hipSuccess) {
-        LMC_LAUNCH(seed_kernel, dim3(e->cfg.chains), dim3(64), 0, main_stream(e), e->A, dseeds);
-        err = hipGetLastError();
+        err = static_cast<hipError_t>(launch(seed_kernel, dim3(e->cfg.chains), dim3(64), 0, main_stream(e), e->A, dseeds));
         if (err == hipSuccess)
             err = hipMemcpyAsync(e->seeds, dseeds, e->cfg.chains * sizeof(uint32_t), hipMemcpyDeviceToDevice, main_stream(e));
     }
@@ -1899,9 +1850,7 @@ int lmc_engine_set_dual_average(lmc_engine* e, double log_step, double log_bar, 
     if (!e) return fail(nullptr, LMC_ERR_INVALID, "null engine");
     HIP_TRY(e, hipSetDevice(e->cfg.device));
     const int threads = 256, blocks = (e->cfg.chains + threads - 1) / threads;
-    LMC_LAUNCH(set_da_kernel, dim3(blocks), dim3(threads), 0, main_stream(e), e->A, log_step, log_bar, hbar, count);
-    HIP_TRY(e, hipGetLastError());
-    return LMC_OK;
+    return launched(e, launch(set_da_kernel, dim3(blocks), dim3(threads), 0, main_stream(e), e->A, log_step, log_bar, hbar, count));
 }
 
 int lmc_engine_reserve(lmc_engine* e, int64_t capacity, int64_t trace_begin) {
@@ -1997,7 +1946,7 @@ static int wide_run(lmc_engine* e, SamplerParams P) {
     P.chain_begin = 0;
     P.relay_mask = relay_mask_for(e->cfg.chains);
     hipStream_t st = main_stream(e);
-    const bool rtc = e->cfg.target_family == LMC_TARGET_USER && !kUserCompiledInDense;
+    const bool rtc = rtc_user(e->cfg.target_family);
     // while tuning, FullAdapt refreshes covariance and factor after EVERY iteration (quadpotential.py:528-552): one iteration
     // per launch with the update kernel in between, like dense_run(); everything else is one launch
     const long long end = P.iter_begin + P.n_iters;
@@ -2043,7 +1992,7 @@ int lmc_engine_run(lmc_engine* e, int64_t n_tune, int64_t iter_begin, int32_t n_
     // the deep-tree plan exists for the one-wave kernels, and for a run-time compiled density only once its plan-1 kernel has
     // been handed over: anything else launches under plan 0 whatever was chosen (LDS layout and kernel must agree)
     if (e->run_w != 1 || e->lds_bytes1 <= 0 ||
-        (e->cfg.target_family == LMC_TARGET_USER && !kUserCompiledIn && !e->user_run1))
+        (rtc_user(e->cfg.target_family) && !e->user_run1))
         plan = 0;
     e->plan_last = plan;
     if (plan == 1) {   // the deep-tree plan: its own level count, no generator behind the stack
@@ -2054,39 +2003,9 @@ int lmc_engine_run(lmc_engine* e, int64_t n_tune, int64_t iter_begin, int32_t n_
     const dim3 block(64 * e->run_w);
     const int n_sub = e->n_sub;
     HIP_TRY(e, order_sub_blocks_after_main(e));
-#define RUN_PLAN1(NSV, WV, T)                                                                                  \
-    if constexpr (WV == 1) {                                                                                   \
-        if (e->leaf_group != run_leaf_group(NSV, 1))                                                           \
-            LMC_LAUNCH((run_kernel<NSV, 1, T, 0, 1, 2>), grid, block, run_lds, st, e->A, P, e->tparams);       \
-        else                                                                                                   \
-            LMC_LAUNCH((run_kernel<NSV, 1, T, 0, 1>), grid, block, run_lds, st, e->A, P, e->tparams);          \
-    }
-#define RUN_ONE(NSV, WV, T)                                                                                    \
-    if (!found && e->run_ns == NSV && e->run_w == WV) {                                                        \
-        found = true;                                                                                          \
-        if (e->cfg.rng_mode == LMC_RNG_PHILOX) {                                                               \
-            if (run_lds > 64 * 1024)                                                                           \
-                HIP_TRY(e, hipFuncSetAttribute(reinterpret_cast<const void*>(&run_kernel<NSV, WV, T, 1>),      \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, run_lds));          \
-            LMC_LAUNCH((run_kernel<NSV, WV, T, 1>), grid, block, run_lds, st, e->A, P, e->tparams);            \
-        } else if (plan == 1) {                                                                                \
-            RUN_PLAN1(NSV, WV, T)                                                                              \
-        } else if (e->leaf_group != run_leaf_group(NSV, WV)) {                                                 \
-            if constexpr (WV == 1)   /* the pinned pair form (run_lds <= 64 KB at one wave) */                \
-                LMC_LAUNCH((run_kernel<NSV, 1, T, 0, 0, 2>), grid, block, run_lds, st, e->A, P, e->tparams);   \
-        } else {                                                                                               \
-            if (run_lds > 64 * 1024)                                                                           \
-                HIP_TRY(e, hipFuncSetAttribute(reinterpret_cast<const void*>(&run_kernel<NSV, WV, T>),         \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, run_lds));          \
-            LMC_LAUNCH((run_kernel<NSV, WV, T>), grid, block, run_lds, st, e->A, P, e->tparams);               \
-        }                                                                                                      \
-    }
-#define RUN_CALL(T)                                                                                            \
-    {                                                                                                          \
-        bool found = false;                                                                                    \
-        LMC_FOR_EACH_SHAPE(RUN_ONE, T)                                                                         \
-        if (!found) return fail(e, LMC_ERR_INVALID, "unsupported kernel shape ns=%d w=%d", e->run_ns, e->run_w); \
-    }
+    const RunKernel kernel = rtc_user(e->cfg.target_family) ? nullptr : sampling_kernel(e, plan);
+    if (!kernel && !rtc_user(e->cfg.target_family))
+        return fail(e, LMC_ERR_INVALID, "unsupported kernel shape ns=%d w=%d", e->run_ns, e->run_w);
     for (int b = 0; b < n_sub; ++b) {
         const long long lo = static_cast<long long>(e->cfg.chains) * b / n_sub, hi = static_cast<long long>(e->cfg.chains) * (b + 1) / n_sub;
         P.chain_begin = static_cast<int>(lo);
@@ -2094,18 +2013,15 @@ int lmc_engine_run(lmc_engine* e, int64_t n_tune, int64_t iter_begin, int32_t n_
         const dim3 grid(static_cast<unsigned>(hi - lo));
         hipStream_t st = n_sub > 1 ? e->sub_stream[b] : main_stream(e);
         if (n_sub > 1) e->sub_pending = true;
-        if (e->cfg.target_family == LMC_TARGET_USER && !kUserCompiledIn) {
+        if (rtc_user(e->cfg.target_family)) {
             void* args[] = {&e->A, &P, &e->tparams};
             const int rc = user_launch(e, plan == 1 ? e->user_run1 : e->user_run, st, grid.x, block.x, static_cast<unsigned>(run_lds), args);
             if (rc != LMC_OK) return rc;
             continue;
         }
-        LMC_FAMILY_SWITCH(e, e->cfg.target_family, RUN_CALL)
+        const int rc = launched(e, launch(kernel, grid, block, run_lds, st, e->A, P, e->tparams));
+        if (rc != LMC_OK) return rc;
     }
-#undef RUN_CALL
-#undef RUN_ONE
-#undef RUN_PLAN1
-    HIP_TRY(e, hipGetLastError());
     HIP_TRY(e, order_external_stream_after_sub_blocks(e));
     return LMC_OK;
 }
@@ -2134,7 +2050,7 @@ int lmc_engine_tick_begin(lmc_engine* e, int64_t n_tune, int64_t iter_begin, int
     e->K.n_tune = n_tune;
     const int rc = e->wide ? tick_wide_launch_begin(e->ns, main_stream(e), e->A, e->K, iter_begin)
                            : tick_launch_begin(e->ns, main_stream(e), e->A, e->K, iter_begin);
-    if (rc != 0) return fail(e, LMC_ERR_HIP, "tick_begin: %s", rc < 0 ? "unsupported vector width" : hipGetErrorString(static_cast<hipError_t>(rc)));
+    if (rc != 0) return fail(e, LMC_ERR_HIP, "tick_begin: %s", rc == kLaunchUnsupported ? "unsupported vector width" : hipGetErrorString(static_cast<hipError_t>(rc)));
     e->ticking = true;
     return LMC_OK;
 }
@@ -2159,7 +2075,7 @@ int lmc_engine_tick(lmc_engine* e, const double* logp, const double* grad, int32
     } else {
         const int rc = e->wide ? tick_wide_launch(e->ns, main_stream(e), e->A, e->K, P, logp, grad)
                                : tick_launch(e->ns, main_stream(e), e->A, e->K, P, logp, grad);
-        if (rc != 0) return fail(e, LMC_ERR_HIP, "tick: %s", rc < 0 ? "unsupported vector width" : hipGetErrorString(static_cast<hipError_t>(rc)));
+        if (rc != 0) return fail(e, LMC_ERR_HIP, "tick: %s", rc == kLaunchUnsupported ? "unsupported vector width" : hipGetErrorString(static_cast<hipError_t>(rc)));
     }
     if (n_active) {
         HIP_TRY(e, hipMemsetAsync(e->K.n_active, 0, sizeof(int), main_stream(e)));
@@ -2213,9 +2129,10 @@ static int gather_stat(lmc_engine* e, void* dst, size_t elem, int kind, int idx,
     DevBuf<char> tmp;
     HIP_TRY(e, tmp.alloc(n * elem));
     hipStream_t st = main_stream(e);
-    LMC_LAUNCH(stat_gather_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, st, e->A.stat_rec, e->A.cap,
-               e->cfg.chains, iter_begin, n_iters, kind, idx, e->cfg.kind == LMC_KIND_HMC ? 1 : 0, static_cast<void*>(tmp.p));
-    HIP_TRY(e, hipGetLastError());
+    const int rc = launched(e, launch(stat_gather_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, st, e->A.stat_rec,
+                                      e->A.cap, e->cfg.chains, iter_begin, n_iters, kind, idx, e->cfg.kind == LMC_KIND_HMC ? 1 : 0,
+                                      static_cast<void*>(tmp.p)));
+    if (rc != LMC_OK) return rc;
     HIP_TRY(e, hipMemcpyAsync(dst, tmp.p, n * elem, hipMemcpyDefault, st));
     HIP_TRY(e, hipStreamSynchronize(st));
     return LMC_OK;
@@ -2343,17 +2260,18 @@ int lmc_engine_copy_window_async(lmc_engine* e, const lmc_window_dst* dst, int64
             const dim3 grid(static_cast<unsigned>(hi - lo < per_grid ? hi - lo : per_grid));
             const bool v2 = row % 2 == 0 && sp % 2 == 0 && dp_ % 2 == 0 && (reinterpret_cast<uintptr_t>(src) % 16 == 0) &&
                             (reinterpret_cast<uintptr_t>(out) % 16 == 0);
-            if (v2) { LMC_LAUNCH(window_trace_copy_kernel<2>, grid, cblock, 0, st, src, sp, out, dp_, row, static_cast<int>(hi - lo)); }
-            else { LMC_LAUNCH(window_trace_copy_kernel<1>, grid, cblock, 0, st, src, sp, out, dp_, row, static_cast<int>(hi - lo)); }
-            HIP_TRY(e, hipGetLastError());
+            const int rc = launched(e, launch(v2 ? window_trace_copy_kernel<2> : window_trace_copy_kernel<1>, grid, cblock, 0, st, src,
+                                              sp, out, dp_, row, static_cast<int>(hi - lo)));
+            if (rc != LMC_OK) return rc;
         }
         if (dst->n_planes > 0) {
             const long long total = (hi - lo) * n;
             long long blocks = (total + kWindowCopyThreads - 1) / kWindowCopyThreads;
             if (blocks > per_grid) blocks = per_grid;
-            LMC_LAUNCH(window_gather_kernel, dim3(static_cast<unsigned>(blocks)), cblock, 0, st, e->A.stat_rec, e->A.cap,
-                       static_cast<int>(lo), static_cast<int>(hi - lo), iter_begin, n_iters, e->cfg.kind == LMC_KIND_HMC ? 1 : 0, W, n_out, row0);
-            HIP_TRY(e, hipGetLastError());
+            const int rc = launched(e, launch(window_gather_kernel, dim3(static_cast<unsigned>(blocks)), cblock, 0, st, e->A.stat_rec,
+                                              e->A.cap, static_cast<int>(lo), static_cast<int>(hi - lo), iter_begin, n_iters,
+                                              e->cfg.kind == LMC_KIND_HMC ? 1 : 0, W, n_out, row0));
+            if (rc != LMC_OK) return rc;
         }
     }
     return LMC_OK;
@@ -2558,8 +2476,9 @@ static int chain_state_xfer(lmc_engine* e, const lmc_chain_state* st, bool to_us
     if ((rc = ints(st->window, A.awindow)) != LMC_OK) return rc;
     if (!to_user && (st->var || st->var64)) {
         const long long n = static_cast<long long>(C) * e->dpad;
-        LMC_LAUNCH(derive_inv_std_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, main_stream(e), e->A, st->var64 ? 1 : 0);
-        HIP_TRY(e, hipGetLastError());
+        rc = launched(e, launch(derive_inv_std_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, main_stream(e), e->A,
+                                st->var64 ? 1 : 0));
+        if (rc != LMC_OK) return rc;
         HIP_TRY(e, hipStreamSynchronize(main_stream(e)));
     }
     return LMC_OK;
@@ -2584,7 +2503,7 @@ int lmc_engine_trajectory(lmc_engine* e, const double* q0, const double* p0, int
     HIP_TRY(e, hipMemcpyAsync(dq0.p, q0, C * d * sizeof(double), hipMemcpyDefault, main_stream(e)));
     HIP_TRY(e, hipMemcpyAsync(dp0.p, p0, C * d * sizeof(double), hipMemcpyDefault, main_stream(e)));
     if (e->wide) {
-        if (e->cfg.target_family == LMC_TARGET_USER && !kUserCompiledInDense) {
+        if (rtc_user(e->cfg.target_family)) {
             int sdot = e->cfg.start_energy_sdot, p32 = p0_is_f32, nf = n_fwd, nb = n_back;
             double eps_ = eps;
             void* args[] = {&e->A, &e->D, &e->tparams, &dq0.p, &dp0.p, &p32, &sdot, &eps_, &nf, &nb, &oq.p, &op.p, &ov.p, &og.p, &oe.p, &ol.p};
@@ -2602,23 +2521,18 @@ int lmc_engine_trajectory(lmc_engine* e, const double* q0, const double* p0, int
                                                e->cfg.start_energy_sdot, eps, n_fwd, n_back, oq.p, op.p, ov.p, og.p,
                                                oe.p, ol.p);
         if (rc != 0) return dense_fail(e, rc, "trajectory");
-    } else {
-    const dim3 grid(e->cfg.chains), block(64);
-    if (e->cfg.target_family == LMC_TARGET_USER && !kUserCompiledIn) {
+    } else if (rtc_user(e->cfg.target_family)) {
         int sdot = e->cfg.start_energy_sdot, p32 = p0_is_f32, nf = n_fwd, nb = n_back;
         double eps_ = eps;
         void* args[] = {&e->A, &e->tparams, &dq0.p, &dp0.p, &p32, &sdot, &eps_, &nf, &nb, &oq.p, &op.p, &ov.p, &og.p, &oe.p, &ol.p};
-        const int rc = user_launch(e, e->user_trajectory, main_stream(e), grid.x, block.x, static_cast<unsigned>(e->dpad * 8), args);
+        const int rc = user_launch(e, e->user_trajectory, main_stream(e), static_cast<unsigned>(e->cfg.chains), 64u,
+                                   static_cast<unsigned>(e->dpad * 8), args);
         if (rc != LMC_OK) return rc;
     } else {
-#define TRAJ_CALL(T)                                                                                          \
-    LMC_NS_SWITCH(e, e->ns, LMC_LAUNCH((trajectory_kernel<NS, T>), grid, block, e->dpad * 8, main_stream(e), e->A,   \
-                                               e->tparams, dq0.p, dp0.p, p0_is_f32, e->cfg.start_energy_sdot, eps, n_fwd, n_back, oq.p, \
-                                               op.p, ov.p, og.p, oe.p, ol.p))
-    LMC_FAMILY_SWITCH(e, e->cfg.target_family, TRAJ_CALL)
-#undef TRAJ_CALL
-    HIP_TRY(e, hipGetLastError());
-    }
+        const auto kernel = with_target(e->cfg.target_family, [&](auto t) { return trajectory_kernel_for(t, e->ns); });
+        const int rc = launched(e, launch(kernel, dim3(e->cfg.chains), dim3(64), e->dpad * 8, main_stream(e), e->A, e->tparams, dq0.p,
+                                          dp0.p, p0_is_f32, e->cfg.start_energy_sdot, eps, n_fwd, n_back, oq.p, op.p, ov.p, og.p, oe.p, ol.p));
+        if (rc != LMC_OK) return rc;
     }
     HIP_TRY(e, hipMemcpyAsync(out_q, oq.p, C * ns * d * sizeof(double), hipMemcpyDefault, main_stream(e)));
     HIP_TRY(e, hipMemcpyAsync(out_p, op.p, C * ns * d * sizeof(double), hipMemcpyDefault, main_stream(e)));
@@ -2638,19 +2552,17 @@ int lmc_engine_logp_dlogp(lmc_engine* e, const double* q, double* logp, double* 
     HIP_TRY(e, dq.alloc(C * d)); HIP_TRY(e, dl.alloc(C)); HIP_TRY(e, dg.alloc(C * d));
     HIP_TRY(e, hipMemcpyAsync(dq.p, q, C * d * sizeof(double), hipMemcpyDefault, main_stream(e)));
     const dim3 grid(e->cfg.chains), block(64);
-    if (e->wide && !(e->cfg.target_family == LMC_TARGET_USER && !kUserCompiledIn)) {
+    if (e->wide && !rtc_user(e->cfg.target_family)) {
         const int rc = wide_launch_logp(e->cfg.target_family, e->ns, e->run_w, main_stream(e), e->A, e->tparams, dq.p, dl.p, dg.p);
         if (rc != 0) return dense_fail(e, rc, "logp_dlogp (general kernel)");
-    } else if (e->cfg.target_family == LMC_TARGET_USER && !kUserCompiledIn) {
+    } else if (rtc_user(e->cfg.target_family)) {
         void* args[] = {&e->A, &e->tparams, &dq.p, &dl.p, &dg.p};
         const int rc = user_launch(e, e->user_logp, main_stream(e), grid.x, e->wide ? 64u * e->run_w : block.x, e->wide ? 2 * 16 * 8 * 8 : 0, args);
         if (rc != LMC_OK) return rc;
     } else {
-#define LOGP_CALL(T) \
-    LMC_NS_SWITCH(e, e->ns, LMC_LAUNCH((logp_kernel<NS, T>), grid, block, 0, main_stream(e), e->A, e->tparams, dq.p, dl.p, dg.p))
-    LMC_FAMILY_SWITCH(e, e->cfg.target_family, LOGP_CALL)
-#undef LOGP_CALL
-    HIP_TRY(e, hipGetLastError());
+        const auto kernel = with_target(e->cfg.target_family, [&](auto t) { return logp_kernel_for(t, e->ns); });
+        const int rc = launched(e, launch(kernel, grid, block, 0, main_stream(e), e->A, e->tparams, dq.p, dl.p, dg.p));
+        if (rc != LMC_OK) return rc;
     }
     HIP_TRY(e, hipMemcpyAsync(logp, dl.p, C * sizeof(double), hipMemcpyDefault, main_stream(e)));
     HIP_TRY(e, hipMemcpyAsync(grad, dg.p, C * d * sizeof(double), hipMemcpyDefault, main_stream(e)));
@@ -2674,8 +2586,9 @@ int lmc_engine_rng_draw(lmc_engine* e, const int32_t* ops, int32_t n_ops, double
     DevBuf<double> dout, dstage;
     HIP_TRY(e, dops.alloc(n_ops)); HIP_TRY(e, dout.alloc(C * total)); HIP_TRY(e, dstage.alloc(C * biggest));
     HIP_TRY(e, hipMemcpyAsync(dops.p, hops.data(), n_ops * sizeof(int32_t), hipMemcpyHostToDevice, main_stream(e)));
-    LMC_LAUNCH(rng_draw_kernel, dim3(e->cfg.chains), dim3(64), 0, main_stream(e), e->A, dops.p, n_ops, dout.p, total, dstage.p, biggest);
-    HIP_TRY(e, hipGetLastError());
+    const int rc = launched(e, launch(rng_draw_kernel, dim3(e->cfg.chains), dim3(64), 0, main_stream(e), e->A, dops.p, n_ops, dout.p,
+                                      total, dstage.p, biggest));
+    if (rc != LMC_OK) return rc;
     HIP_TRY(e, hipMemcpyAsync(out, dout.p, C * total * sizeof(double), hipMemcpyDefault, main_stream(e)));
     HIP_TRY(e, hipStreamSynchronize(main_stream(e)));
     return LMC_OK;
@@ -2698,8 +2611,9 @@ int lmc_engine_draw_momentum(lmc_engine* e, double* out) {
         const int f32 = e->cfg.potential == LMC_POT_DIAG_ADAPT;
         const dim3 grid(e->cfg.chains), block(64);
         const int lds = 2 * e->dpad * 8;
-        LMC_NS_SWITCH(e, e->ns, LMC_LAUNCH((momentum_kernel<NS>), grid, block, lds, main_stream(e), e->A, f32, dout.p))
-        HIP_TRY(e, hipGetLastError());
+        const auto kernel = with_int<1, 2, 4, 8, 16>(e->ns, [](auto NS) { return &momentum_kernel<NS>; });
+        const int rc = launched(e, launch(kernel, grid, block, lds, main_stream(e), e->A, f32, dout.p));
+        if (rc != LMC_OK) return rc;
     }
     HIP_TRY(e, hipMemcpyAsync(out, dout.p, C * d * sizeof(double), hipMemcpyDefault, main_stream(e)));
     HIP_TRY(e, hipStreamSynchronize(main_stream(e)));

@@ -2,6 +2,7 @@
 #include <hip/hip_runtime.h>
 
 #include "lmc_tick.hpp"
+#include "lmc_dispatch.hpp"
 
 namespace lmc {
 
@@ -22,38 +23,17 @@ __global__ __launch_bounds__(256) void tick_count_kernel(TickArrays K, int chain
 
 int tick_launch(int ns, hipStream_t stream, const ChainArrays& A, const TickArrays& K, const SamplerParams& P,
                 const double* logp, const double* grad) {
-    const dim3 grid(A.chains), block(64);
-    const int lds = 2 * A.dpad * 8;
-    (void)hipGetLastError();
-    switch (ns) {
-        case 1: hipLaunchKernelGGL((tick_kernel<1>), grid, block, lds, stream, A, K, P, logp, grad); break;
-        case 2: hipLaunchKernelGGL((tick_kernel<2>), grid, block, lds, stream, A, K, P, logp, grad); break;
-        case 4: hipLaunchKernelGGL((tick_kernel<4>), grid, block, lds, stream, A, K, P, logp, grad); break;
-        case 8: hipLaunchKernelGGL((tick_kernel<8>), grid, block, lds, stream, A, K, P, logp, grad); break;
-        case 16: hipLaunchKernelGGL((tick_kernel<16>), grid, block, lds, stream, A, K, P, logp, grad); break;
-        default: return -1;
-    }
-    return static_cast<int>(hipGetLastError());
+    const auto kernel = with_int<1, 2, 4, 8, 16>(ns, [](auto NS) { return &tick_kernel<NS>; });
+    return launch(kernel, dim3(A.chains), dim3(64), 2 * A.dpad * 8, stream, A, K, P, logp, grad);
 }
 
 int tick_launch_begin(int ns, hipStream_t stream, const ChainArrays& A, const TickArrays& K, long long iter_begin) {
-    const dim3 grid(A.chains), block(64);
-    (void)hipGetLastError();
-    switch (ns) {
-        case 1: hipLaunchKernelGGL((tick_begin_kernel<1>), grid, block, 0, stream, A, K, iter_begin); break;
-        case 2: hipLaunchKernelGGL((tick_begin_kernel<2>), grid, block, 0, stream, A, K, iter_begin); break;
-        case 4: hipLaunchKernelGGL((tick_begin_kernel<4>), grid, block, 0, stream, A, K, iter_begin); break;
-        case 8: hipLaunchKernelGGL((tick_begin_kernel<8>), grid, block, 0, stream, A, K, iter_begin); break;
-        case 16: hipLaunchKernelGGL((tick_begin_kernel<16>), grid, block, 0, stream, A, K, iter_begin); break;
-        default: return -1;
-    }
-    return static_cast<int>(hipGetLastError());
+    const auto kernel = with_int<1, 2, 4, 8, 16>(ns, [](auto NS) { return &tick_begin_kernel<NS>; });
+    return launch(kernel, dim3(A.chains), dim3(64), 0, stream, A, K, iter_begin);
 }
 
 int tick_launch_count(hipStream_t stream, const TickArrays& K, int chains) {
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(tick_count_kernel, dim3((chains + 255) / 256), dim3(256), 0, stream, K, chains);
-    return static_cast<int>(hipGetLastError());
+    return launch(tick_count_kernel, dim3((chains + 255) / 256), dim3(256), 0, stream, K, chains);
 }
 
 }  // namespace lmc

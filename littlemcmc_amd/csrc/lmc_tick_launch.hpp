@@ -1,5 +1,5 @@
 // Host-callable launchers of the tick kernels (lmc_tick.hip); called by the C ABI in lmc_engine.hip.
-// Return value: 0 = launched, -1 = unsupported vector width, otherwise a hipError_t.
+// Return value: that of launch() (lmc_dispatch.hpp).
 #pragma once
 #include <hip/hip_runtime.h>
 

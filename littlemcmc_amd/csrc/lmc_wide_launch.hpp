@@ -1,5 +1,5 @@
 // Host-callable launchers of the general ("wide") kernels (lmc_wide.hip); called by the C ABI in lmc_engine.hip.
-// Return value: 0 = launched, kWideUnsupported = no such instantiation in this build, otherwise a hipError_t.
+// Return value: that of launch() (lmc_dispatch.hpp).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -7,7 +7,6 @@
 
 namespace lmc {
 
-constexpr int kWideUnsupported = -1;
 constexpr int kWideBlock = 1024;        // threads per chain of the large team (16 wavefronts)
 constexpr int kWideMaxDim = 16384;      // 1024 threads x 16 elements
 constexpr int kWideOneWaveMaxDim = 512;  // one wavefront per chain up to here (8 elements per lane), the 16-wavefront team beyond
