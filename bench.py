@@ -3,6 +3,13 @@
 
     python bench.py --gpus N --steps K --warmup W            (N = 1: this process)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+    python bench.py --full ...                               (everything below, not only the headline)
+
+A plain run does only what the headline needs: it sets up, warms up, times the K steps, writes --dump-outputs if asked and
+prints the line (headline fields, config, the roofline and tail figures read off the timed job itself). Whatever takes work
+of its own -- ESS / R-hat of the draws, the lone-chain latency of the tail block, the one-rank RCCL check at N = 1, the
+secondary workloads, sample_e2e and the CPU baseline -- runs only with --full, where the --no-* options leave parts out.
+Either way the timed job is the same: its draws stay in HBM (--no-trace aside) whether or not ESS is computed from them.
 
 Workload (BASELINE.json configs[2] / SURVEY.md 8d "C3"): 65 536 chains x dim 128, AR(1) rho=0.9 correlated
 Gaussian, NUTS defaults, diagonal mass adaptation, init jitter+adapt_diag; the timed job is the reference recipe
@@ -23,16 +30,16 @@ roofline         = the bound that binds the kernel: FP64 vector issue. achieved 
                    so they are not a bound. Counter-derived fields (HBM traffic, VALU instructions per leapfrog) are
                    quoted from profiles/pmc_counters.json ONLY if that profile was taken on this very build
                    (source hash match); otherwise they are null.
-secondary        = north_star's named shape (standard normal, d = 128, same chains / recipe) in both RNG modes and, on the
-                   default command line, the other BASELINE.json configurations -- C2 (4 096 x 64), C4 (8 192 x 1000),
+secondary        = (--full) north_star's named shape (standard normal, d = 128, same chains / recipe) in both RNG modes and,
+                   for the default workload, the other BASELINE.json configurations -- C2 (4 096 x 64), C4 (8 192 x 1000),
                    C5 (16 384 x 256 funnel, treedepth 12; as K launches and as ONE launch) -- each timed the same way with
                    its own roofline and tail block.
 stdout           = ONE compact JSON line (compact_line(): <= 8192 bytes -- headline fields, config, roofline, cpu_baseline, ESS
                    numbers, a short block per secondary workload); the verbose object (every note, full secondary blocks)
                    is written to bench_detail.json (--detail-out), not to stderr.
-sample_e2e       = the literal drop-in call lmc.sample(...) -> numpy arrays on C3's chains (tune 300 + draws 200), wall time next to
-                   the kernel-only time of the same job (N = 1, default command line).
-cpu_baseline     = the numpy oracle (a port of the reference, oracle/lmc_oracle.py) on this box's host cores, one chain
+sample_e2e       = (--full) the literal drop-in call lmc.sample(...) -> numpy arrays on C3's chains (tune 300 + draws 200), wall
+                   time next to the kernel-only time of the same job (N = 1, default workload).
+cpu_baseline     = (--full) the numpy oracle (a port of the reference, oracle/lmc_oracle.py) on this box's host cores, one chain
                    per core, same recipe, bounded sample.
 """
 import argparse
@@ -356,7 +363,7 @@ def self_launch(n):
     return subprocess.call(cmd, env=env)
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
@@ -405,7 +412,19 @@ def main():
                          "lmc.sample(..., devices=[...]) does); no process group, so a RCCL / launcher bring-up failure "
                          "cannot cost the scaling curve. The line records which one ran (`launcher`). If there are fewer "
                          "GPUs than N (the one-GPU test box) the engines share devices round-robin.")
-    args = ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: ESS / R-hat of the draws, the lone-chain "
+                         "latency of the tail block, the one-rank RCCL check (N = 1), the secondary workloads, sample_e2e and "
+                         "the CPU baseline; the --no-* options leave parts of it out. Without it a run times the headline job only")
+    args = ap.parse_args(argv)
+    if not args.full:
+        for extra in ("no_rccl_check", "no_tail", "no_ess", "no_secondary", "no_e2e", "no_cpu_baseline"):
+            setattr(args, extra, True)
+    return args
+
+
+def main():
+    args = parse_args()
 
     inproc = args.launcher == "inproc"
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and not inproc:
@@ -684,7 +703,8 @@ def main():
                 w_.synchronize()
                 w_.close()
 
-        # draws stay in HBM; if the requested job is longer than the memory allows, keep the most recent draws only
+        # draws stay in HBM; if the requested job is longer than the memory allows, keep the most recent draws only. They are
+        # kept whether or not ESS is computed from them (--no-ess, a plain run), so the timed job is the same either way
         trace_begin = n_tune
         keep_trace = with_ess and not args.no_trace
         if keep_trace:

@@ -26,8 +26,8 @@ def test_bench_launches_its_own_ranks_and_the_blocks_add_up():
     """`python bench.py --gpus 2` with no launcher and no WORLD_SIZE: bench.py re-runs itself as 2 ranks under
     torch.distributed.run (gloo here: two ranks share this one GPU), prints one line, exits 0 -- and the two chain blocks
     together did exactly the leapfrogs of the one-process job (same global seeds, strong scaling)."""
-    one = run_bench(["--gpus", "1"])
-    two = run_bench(["--gpus", "2", "--backend", "gloo"])
+    one = run_bench(["--gpus", "1", "--full"])
+    two = run_bench(["--gpus", "2", "--backend", "gloo", "--full"])
     assert one["n_gpus"] == 1 and two["n_gpus"] == 2
     assert two["leapfrogs"] == one["leapfrogs"]
     assert [r["chains"] for r in two["per_rank"]] == [256, 256]
@@ -43,6 +43,23 @@ def test_bench_launches_its_own_ranks_and_the_blocks_add_up():
     # N = 1 under the default backend brings up a one-rank RCCL group and says so in the line
     assert one["backend"] == "nccl" and (one["rccl_ranks"] == 1 or one["rccl_error"])
     assert one["rccl_ranks"] == 1, one["rccl_error"]
+
+
+def test_plain_run_times_the_same_job_and_nothing_else():
+    """Without --full a run times the same job and prints the same headline, and runs nothing that the headline does not
+    need: no ESS, no lone-chain latency in the tail block, no one-rank RCCL group, no secondary, sample_e2e or CPU baseline."""
+    plain = run_bench(["--gpus", "1"])
+    full = run_bench(["--gpus", "1", "--full"])
+    for key in ("metric", "unit", "higher_is_better", "dtype", "n_gpus", "steps", "warmup", "config", "leapfrogs",
+                "mean_depth_draws", "divergences_after_tune"):
+        assert plain[key] == full[key], key
+    assert plain["value"] > 0 and plain["ms_per_step"] > 0 and plain["roofline"]["kernel_ms_avg"] > 0
+    assert plain["ess_per_sec"] is None and full["ess_per_sec"]["ess_min"] > 0
+    assert "lone_wave_us_per_leapfrog" not in plain["tail"] and full["tail"]["lone_wave_us_per_leapfrog"] > 0
+    assert plain["tail"]["busiest_chain_leapfrogs"] == full["tail"]["busiest_chain_leapfrogs"]
+    assert plain["rccl_ranks"] is None and plain["rccl_error"] is None and full["rccl_ranks"] == 1
+    for key in ("cpu_baseline", "sample_e2e", "secondary"):
+        assert key not in plain, key
 
 
 def test_bench_under_torchrun_still_works():

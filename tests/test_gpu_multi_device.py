@@ -126,8 +126,8 @@ def test_bench_inproc_launcher_adds_up_to_the_one_gpu_job():
     """`bench.py --gpus 2 --launcher inproc`: the second way to produce the scaling curve -- one process, one engine per
     GPU, no process group -- does exactly the leapfrogs of the N = 1 job (same global seeds, strong scaling) and says in
     the line which launcher ran."""
-    one = _bench(["--gpus", "1", "--no-rccl-check"])
-    two = _bench(["--gpus", "2", "--launcher", "inproc"])
+    one = _bench(["--gpus", "1", "--no-rccl-check", "--full"])
+    two = _bench(["--gpus", "2", "--launcher", "inproc", "--full"])
     assert (one["n_gpus"], two["n_gpus"]) == (1, 2)
     assert two["leapfrogs"] == one["leapfrogs"]
     assert [r["chains"] for r in two["per_rank"]] == [256, 256]

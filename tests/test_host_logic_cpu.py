@@ -623,3 +623,21 @@ def test_bench_dump_plan_is_fixed_and_bounded():
         assert total < 64e6, (chains, dim, ips, total)
     idx, n_it = bench.dump_plan(65536, 128, 100, n_stats)
     assert n_it == 100 and len(idx) >= 256    # the headline's last step whole, for a few hundred chains
+
+
+def test_bench_plain_run_leaves_the_extras_to_full():
+    """A plain bench.py run times the headline job only; --full brings back everything else, and the --no-* options still
+    leave parts of a --full run out. The timed job itself (its steps, warm-up and kept draws) does not depend on --full."""
+    import importlib
+
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+    extras = ("no_rccl_check", "no_tail", "no_ess", "no_secondary", "no_e2e", "no_cpu_baseline")
+    plain = bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    full = bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1", "--full"])
+    assert not plain.full and all(getattr(plain, k) for k in extras)
+    assert full.full and not any(getattr(full, k) for k in extras)
+    part = bench.parse_args(["--full", "--no-cpu-baseline", "--no-secondary"])
+    assert part.no_cpu_baseline and part.no_secondary and not (part.no_ess or part.no_tail or part.no_e2e)
+    same = ("steps", "warmup", "no_trace", "chains", "iters_per_step", "target", "dim", "rng", "dump_outputs")
+    assert all(getattr(plain, k) == getattr(full, k) for k in same) and not plain.no_trace

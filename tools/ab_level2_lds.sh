@@ -7,5 +7,5 @@
 L=${LIBS:-"build_variants/liblmc_base.so build_variants/liblmc_l2lds.so build_variants/liblmc_l2lds2.so"}
 if [ $# -eq 0 ]; then set -- "" "--target std_normal"; fi
 for args in "$@"; do for i in 1 2; do for lib in $L; do
-r=$(LMC_HIP_LIB=$lib timeout 600 python bench.py $args --no-cpu-baseline --no-ess --no-secondary --no-rccl-check 2>/dev/null | grep metric | python -c "import json,sys; d=json.loads(sys.stdin.read()); t=d['tail']; print('%.4e kernel_ms %.2f lds %d resident %d lone %.3f us' % (d['value'], d['roofline']['kernel_ms_avg'], t['lds_bytes_per_workgroup'], t['resident_chains'], t['lone_wave_us_per_leapfrog']))")
+r=$(LMC_HIP_LIB=$lib timeout 600 python bench.py $args --full --no-cpu-baseline --no-ess --no-secondary --no-rccl-check 2>/dev/null | grep metric | python -c "import json,sys; d=json.loads(sys.stdin.read()); t=d['tail']; print('%.4e kernel_ms %.2f lds %d resident %d lone %.3f us' % (d['value'], d['roofline']['kernel_ms_avg'], t['lds_bytes_per_workgroup'], t['resident_chains'], t['lone_wave_us_per_leapfrog']))")
 echo "$(basename $lib) [$args]: $r"; done; done; done

@@ -13,6 +13,6 @@ bash tools/reprofile.sh ${tag}prof $tag > $out/reprofile.log 2>&1
   echo "== tools/fuzz_paths.py 300 777"; python tools/fuzz_paths.py 300 777 | tail -3 ) > $out/fuzz.txt 2>&1
 python tools/sample_e2e.py c3 65536 1000 1000 1 > $out/e2e_c3.txt 2>&1
 python tools/sample_e2e.py c2 > $out/e2e_c2.txt 2>&1
-python bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench_driver_form.json 2> $out/bench_driver_form.err
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $out/bench_driver_form.json 2> $out/bench_driver_form.err
 cp bench_detail.json $out/bench_detail_driver_form.json
 cat $out/gpu_suite.txt $out/smoke.txt $out/fuzz.txt; grep -h "best\|run " $out/e2e_c3.txt $out/e2e_c2.txt

@@ -6,7 +6,7 @@ out=$1; shift
 echo "[" > $out
 first=1
 for c in 65536 32768 16384 8192; do
-  line=$(timeout 600 python bench.py --chains $c --no-cpu-baseline --no-secondary --no-rccl-check "$@" 2>/dev/null | grep '"metric"')
+  line=$(timeout 600 python bench.py --full --chains $c --no-cpu-baseline --no-secondary --no-rccl-check "$@" 2>/dev/null | grep '"metric"')
   [ $first = 1 ] || echo "," >> $out
   first=0
   echo "$line" | python -c "

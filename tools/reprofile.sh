@@ -10,9 +10,9 @@ bash tools/summarize_all.sh $out $tag >> gpurun_out/$out.summary.txt 2>&1
 L=gpurun_out/$out/lines
 mkdir -p $L
 line() { grep '"metric"' | head -1; }
-timeout 900 python bench.py 2>/dev/null | line > $L/bench_default_line.json
-timeout 900 python bench.py --gpus 2 --launcher inproc --no-cpu-baseline 2>/dev/null | line > $L/bench_inproc_2_engines_one_gpu.json
-B="--no-cpu-baseline --no-secondary --no-rccl-check"
+timeout 900 python bench.py --full 2>/dev/null | line > $L/bench_default_line.json
+timeout 900 python bench.py --full --gpus 2 --launcher inproc --no-cpu-baseline 2>/dev/null | line > $L/bench_inproc_2_engines_one_gpu.json
+B="--full --no-cpu-baseline --no-secondary --no-rccl-check"
 timeout 600 python bench.py $B --target diag --dim 1000 --chains 8192 2>/dev/null | line > $L/c4_bench.json
 timeout 600 python bench.py $B --target diag --dim 1000 --chains 8192 --rng philox 2>/dev/null | line > $L/c4_philox_bench.json
 timeout 600 python bench.py $B --target funnel --dim 256 --chains 16384 --max-treedepth 12 --steps 1 --iters-per-step 2000 --warmup 0 2>/dev/null | line > $L/c5_one_launch_bench.json
