@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define LMC_ABI_VERSION 8
+#define LMC_ABI_VERSION 9
 
 /* status codes */
 #define LMC_OK 0
@@ -194,7 +194,8 @@ typedef struct lmc_config {
  * QuadPotentialDiagAdapt / QuadPotentialFullAdapt(dtype="float64") -- runs in the GENERAL kernels (csrc/lmc_wide.hpp: one
  * chain = one wavefront up to dim 512, a workgroup of 16 wavefronts beyond, the tree in the chain's HBM row): the same
  * algorithm, statement for statement, several times slower per leapfrog. Not in the general kernels: LMC_RNG_PHILOX, and LMC_TARGET_EXTERNAL with
- * anything but a float32 diagonal. */
+ * anything but a float32 diagonal. A shared matrix adapted from all chains (lmc_engine_pool_*, LMC_POT_FULL up to dim 256) samples
+ * in the LMC_POT_FULL kernels; its statistic is formed by pool_accumulate_kernel (csrc/lmc_pool.hip) on the matrix cores. */
 /* Fill *cfg with the reference's defaults for the given shape. */
 void lmc_config_defaults(lmc_config* cfg, int32_t chains, int32_t dim);
 
@@ -457,6 +458,29 @@ int lmc_engine_get_dense_factor_f64(lmc_engine* e, double* chol);
 /* Test entry: potential.update(sample = current position, grad, tune) for every chain (quadpotential.py:528-552).
  * During lmc_engine_run() the same kernel runs after every tuning iteration. */
 int lmc_engine_dense_update(lmc_engine* e, int32_t tune);
+
+/* ---- one shared dense matrix adapted from ALL chains (LMC_POT_FULL, dim <= 256, fused kernels; other potentials:
+ * LMC_ERR_STATE, larger dim: LMC_ERR_INVALID). The reference has no such estimator: its adaptive dense potential learns one
+ * matrix per chain from that chain's own draws (quadpotential.py:471-557); with C chains one iteration already holds C draws of
+ * the target. The engine keeps, in float64 on the device,
+ *     n,  shift[dim],  s = sum (q - shift),  S = sum (q - shift)(q - shift)^T
+ * over SNAPSHOTS of the current positions of all chains; shift is the column mean of the first snapshot after a reset, so that
+ * S - s s^T / n has no cancellation to speak of. The sums are formed without floating-point atomics in an order that depends
+ * on the chain count alone: the same positions give the same bits.
+ * pool_reset():      zero the statistic. Asynchronous.
+ * pool_accumulate(): one snapshot. Asynchronous: ordered after every lmc_engine_run() enqueued so far, and the next
+ *                    lmc_engine_run() is ordered after it; the host does not wait. At least 2 chains.
+ * pool_get():        synchronises. n, mean = shift + s / n [dim], m2 = S - s s^T / n [dim][dim] (symmetric). Any pointer may be NULL.
+ * pool_apply():      synchronises. cov = m2 / (n - 1), shrunk as Stan does, cov <- n / (n + 5) cov + 1e-3 * 5 / (n + 5) I, then
+ *                    installed as the engine's shared matrix exactly as lmc_engine_set_dense_potential(cov) installs one.
+ *                    n < 2, a non-finite entry or a failed factorisation: LMC_ERR_INVALID, the installed matrix stays.
+ * restart_dual_average(): per chain mu <- log(10 exp(log_step)), hbar <- 0, log_bar <- 0, count <- 1 (log_step stays): Stan's
+ *                    restart of step-size adaptation after a change of metric. Asynchronous. */
+int lmc_engine_pool_reset(lmc_engine* e);
+int lmc_engine_pool_accumulate(lmc_engine* e);
+int lmc_engine_pool_get(lmc_engine* e, int64_t* n, double* mean, double* m2);
+int lmc_engine_pool_apply(lmc_engine* e);
+int lmc_engine_restart_dual_average(lmc_engine* e);
 
 /* ---- externally evaluated density (cfg.target_family = LMC_TARGET_EXTERNAL): the iteration loop of
  * sampling.py:507-521 / base_hmc.py:140-190 cut at the two places the reference calls logp_dlogp_func

@@ -18,7 +18,8 @@ quad_potential = _qp.quad_potential
 QuadPotentialDiag, QuadPotentialDiagAdapt = _qp.QuadPotentialDiag, _qp.QuadPotentialDiagAdapt
 QuadPotentialFull, QuadPotentialFullInv, QuadPotentialFullAdapt = (
     _qp.QuadPotentialFull, _qp.QuadPotentialFullInv, _qp.QuadPotentialFullAdapt)
+QuadPotentialFullPooled = _qp.QuadPotentialFullPooled   # one shared matrix adapted from all chains during tuning
 
 __all__ = ["sample", "init_nuts", "HamiltonianMC", "NUTS", "quad_potential", "QuadPotentialDiag", "QuadPotentialFull",
-           "QuadPotentialFullInv", "QuadPotentialDiagAdapt", "QuadPotentialFullAdapt", "Engine", "StepRandUniform", "targets",
+           "QuadPotentialFullInv", "QuadPotentialDiagAdapt", "QuadPotentialFullAdapt", "QuadPotentialFullPooled", "Engine", "StepRandUniform", "targets",
            "diagnostics", "distributed"]

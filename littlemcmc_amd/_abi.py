@@ -11,7 +11,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LMC_HIP_LIB") or os.path.join(_HERE, "liblmc_hip.so")
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 OK = 0
 
 KIND_NUTS, KIND_HMC = 0, 1
@@ -117,6 +117,11 @@ _SIGNATURES = {
     "lmc_engine_get_dense_state": (C.c_int, [_P, C.POINTER(DenseState)]),
     "lmc_engine_set_dense_state": (C.c_int, [_P, C.POINTER(DenseState)]),
     "lmc_engine_dense_update": (C.c_int, [_P, C.c_int32]),
+    "lmc_engine_pool_reset": (C.c_int, [_P]),
+    "lmc_engine_pool_accumulate": (C.c_int, [_P]),
+    "lmc_engine_pool_get": (C.c_int, [_P, C.POINTER(C.c_int64), _P, _P]),
+    "lmc_engine_pool_apply": (C.c_int, [_P]),
+    "lmc_engine_restart_dual_average": (C.c_int, [_P]),
     "lmc_engine_tick_begin": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int32]),
     "lmc_engine_tick_positions": (_P, [_P]),
     "lmc_engine_tick": (C.c_int, [_P, _P, _P, C.POINTER(C.c_int32)]),

@@ -19,6 +19,7 @@
 #include "lmc_dense_launch.hpp"
 #include "lmc_tick_launch.hpp"
 #include "lmc_wide_launch.hpp"
+#include "lmc_pool.hpp"
 #include "lmc_dispatch.hpp"
 
 using namespace lmc;
@@ -362,6 +363,10 @@ struct lmc_engine {
     TickArrays K;
     bool ticking = false;
     int* adapt_mask = nullptr;     // [C] chains whose FullAdapt.update is due after the current tick
+    // second moment of the positions of all chains (lmc_engine_pool_*, LMC_POT_FULL): allocated by the first call that needs it
+    PoolArrays pool = {};
+    bool pool_ready = false;
+    bool pool_shifted = false;     // a snapshot since the last reset has fixed pool.shift
     // run-time compiled user density (cfg.target_family == LMC_TARGET_USER in the stock library): the three kernels that
     // depend on the density functor come from a code object the caller compiled with hiprtc
     hipModule_t user_module = nullptr;
@@ -488,6 +493,55 @@ static bool host_cholesky(std::vector<T>& a, int d) {   // a: [d][d] row-major, 
     for (int i = 0; i < d; ++i)
         for (int j = i + 1; j < d; ++j) a[static_cast<size_t>(i) * d + j] = T(0);
     return true;
+}
+
+// QuadPotentialFull / FullAdapt: the float32 covariance and its lower Cholesky factor (quadpotential.py:441-443) in the
+// layout the device holds them: covT [d][dpad] (transposed), fac [d8][dpad] (padding rows: identity). false: not positive definite.
+struct DenseF32 {
+    std::vector<float> L, covT, fac;
+};
+static bool dense_f32_factor(const lmc_engine* e, const std::vector<double>& m, DenseF32& f) {
+    const int d = e->cfg.dim, dp = e->dpad, d8 = e->d8;
+    const size_t dd = static_cast<size_t>(d) * d;
+    std::vector<float> cov(dd);
+    for (size_t i = 0; i < dd; ++i) cov[i] = static_cast<float>(m[i]);
+    f.L = cov;
+    if (!host_cholesky(f.L, d)) return false;
+    f.covT.assign(static_cast<size_t>(d) * dp, 0.0f);
+    f.fac.assign(static_cast<size_t>(d8) * dp, 0.0f);
+    for (int i = 0; i < d; ++i)
+        for (int j = 0; j < d; ++j) {
+            f.covT[static_cast<size_t>(j) * dp + i] = cov[static_cast<size_t>(i) * d + j];
+            f.fac[static_cast<size_t>(i) * dp + j] = f.L[static_cast<size_t>(i) * d + j];
+        }
+    for (int i = d; i < d8; ++i) f.fac[static_cast<size_t>(i) * dp + i] = 1.0f;   // padding rows: identity
+    return true;
+}
+
+// LMC_POT_FULL: make `m` ([dim][dim], finite) the engine's shared covariance -- float32 rounding, factorisation, L^-1 in
+// extended precision for the coop kernel's momentum draw (lmc_dense_types.hpp), the three uploads. The one tail of
+// lmc_engine_set_dense_potential() and lmc_engine_pool_apply(); nothing is uploaded unless the matrix factorises. The
+// caller has synchronised the engine.
+static int install_full(lmc_engine* e, const std::vector<double>& m) {
+    const int d = e->cfg.dim, dp = e->dpad;
+    const size_t dd = static_cast<size_t>(d) * d;
+    DenseF32 f;
+    if (!dense_f32_factor(e, m, f)) return fail(e, LMC_ERR_INVALID, "matrix is not positive definite");
+    const std::vector<float>& L = f.L;
+    std::vector<long double> Li(dd, 0.0L);
+    for (int c = 0; c < d; ++c)
+        for (int i = c; i < d; ++i) {
+            long double acc = (i == c) ? 1.0L : 0.0L;
+            for (int k = c; k < i; ++k) acc -= static_cast<long double>(L[static_cast<size_t>(i) * d + k]) * Li[static_cast<size_t>(k) * d + c];
+            Li[static_cast<size_t>(i) * d + c] = acc / static_cast<long double>(L[static_cast<size_t>(i) * d + i]);
+        }
+    std::vector<double> finv(static_cast<size_t>(sweep_rows(d)) * dp, 0.0);
+    for (int k = 0; k < d; ++k)
+        for (int i = 0; i <= k; ++i) finv[static_cast<size_t>(k) * dp + i] = static_cast<double>(Li[static_cast<size_t>(k) * d + i]);
+    HIP_TRY(e, hipMemcpy(e->D.covT, f.covT.data(), f.covT.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(e, hipMemcpy(e->D.fac, f.fac.data(), f.fac.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(e, hipMemcpy(const_cast<double*>(e->D.fac_inv), finv.data(), finv.size() * sizeof(double), hipMemcpyHostToDevice));
+    return LMC_OK;
 }
 
 static int dense_reset(lmc_engine* e) {   // FULL_ADAPT: constructor state for every chain
@@ -1473,38 +1527,15 @@ int lmc_engine_set_dense_potential(lmc_engine* e, const double* matrix, const do
         HIP_TRY(e, hipStreamSynchronize(main_stream(e)));
         return LMC_OK;
     }
-    // QuadPotentialFull / FullAdapt: float32 covariance and its lower Cholesky factor (quadpotential.py:441-443)
-    std::vector<float> cov(dd);
-    for (size_t i = 0; i < dd; ++i) cov[i] = static_cast<float>(m[i]);
-    std::vector<float> L(cov);
-    if (!host_cholesky(L, d)) return fail(e, LMC_ERR_INVALID, "matrix is not positive definite");
-    std::vector<float> covT(static_cast<size_t>(d) * dp, 0.0f), fac(static_cast<size_t>(d8) * dp, 0.0f);
+    if (e->cfg.potential == LMC_POT_FULL) return install_full(e, m);
+    DenseF32 f;
+    if (!dense_f32_factor(e, m, f)) return fail(e, LMC_ERR_INVALID, "matrix is not positive definite");
+    const std::vector<float>& covT = f.covT;
+    const std::vector<float>& fac = f.fac;
     std::vector<double> rawT(static_cast<size_t>(d) * dp, 0.0), mean_p(dp, 0.0);
     for (int i = 0; i < d; ++i) {
         mean_p[i] = mean[i];
-        for (int j = 0; j < d; ++j) {
-            covT[static_cast<size_t>(j) * dp + i] = cov[static_cast<size_t>(i) * d + j];
-            rawT[static_cast<size_t>(j) * dp + i] = m[static_cast<size_t>(i) * d + j];      // float64 initial_cov (:506-508)
-            fac[static_cast<size_t>(i) * dp + j] = L[static_cast<size_t>(i) * d + j];
-        }
-    }
-    for (int i = d; i < d8; ++i) fac[static_cast<size_t>(i) * dp + i] = 1.0f;   // padding rows: identity
-    if (e->cfg.potential == LMC_POT_FULL) {
-        HIP_TRY(e, hipMemcpy(e->D.covT, covT.data(), covT.size() * sizeof(float), hipMemcpyHostToDevice));
-        HIP_TRY(e, hipMemcpy(e->D.fac, fac.data(), fac.size() * sizeof(float), hipMemcpyHostToDevice));
-        // L^-1 of the float32 factor, extended precision, for the coop kernel's momentum draw (lmc_dense_types.hpp)
-        std::vector<long double> Li(dd, 0.0L);
-        for (int c = 0; c < d; ++c)
-            for (int i = c; i < d; ++i) {
-                long double acc = (i == c) ? 1.0L : 0.0L;
-                for (int k = c; k < i; ++k) acc -= static_cast<long double>(L[static_cast<size_t>(i) * d + k]) * Li[static_cast<size_t>(k) * d + c];
-                Li[static_cast<size_t>(i) * d + c] = acc / static_cast<long double>(L[static_cast<size_t>(i) * d + i]);
-            }
-        std::vector<double> finv(static_cast<size_t>(sweep_rows(d)) * dp, 0.0);
-        for (int k = 0; k < d; ++k)
-            for (int i = 0; i <= k; ++i) finv[static_cast<size_t>(k) * dp + i] = static_cast<double>(Li[static_cast<size_t>(k) * d + i]);
-        HIP_TRY(e, hipMemcpy(const_cast<double*>(e->D.fac_inv), finv.data(), finv.size() * sizeof(double), hipMemcpyHostToDevice));
-        return LMC_OK;
+        for (int j = 0; j < d; ++j) rawT[static_cast<size_t>(j) * dp + i] = m[static_cast<size_t>(i) * d + j];      // float64 initial_cov (:506-508)
     }
     if (adaptation_window < 1 || update_window < 1 || !(adaptation_window_multiplier > 0.0) || initial_weight < 0.0)
         return fail(e, LMC_ERR_INVALID, "bad FullAdapt parameters");
@@ -1530,6 +1561,134 @@ int lmc_engine_dense_update(lmc_engine* e, int32_t tune) {
     const int rc = dense_launch_adapt(main_stream(e), e->A, e->D, e->dense_multiplier, e->dense_update_window);
     if (rc != 0) return dense_fail(e, rc, "dense update");
     return LMC_OK;
+}
+
+// ---- pooled second moment of all chains (LMC_POT_FULL): the statistic a shared dense matrix is adapted from -------------
+static int pool_check(lmc_engine* e) {
+    if (!e) return fail(nullptr, LMC_ERR_INVALID, "null engine");
+    if (e->cfg.potential != LMC_POT_FULL)
+        return fail(e, LMC_ERR_STATE, "the pooled covariance belongs to a float32 shared dense matrix (cfg.potential = LMC_POT_FULL, got %d)",
+                    e->cfg.potential);
+    if (e->cfg.dim > kPoolMaxDpad || e->wide)
+        return fail(e, LMC_ERR_INVALID, "pooled dense mass matrices run on the device up to model_ndim = %d in the fused kernels (got %d)",
+                    kPoolMaxDpad, e->cfg.dim);
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    return LMC_OK;
+}
+
+static int pool_ensure(lmc_engine* e) {
+    const int ok = pool_check(e);
+    if (ok != LMC_OK) return ok;
+    if (e->pool_ready) return LMC_OK;
+    PoolArrays& P = e->pool;
+    P.dpad = e->dpad;
+    pool_plan(e->cfg.chains, P.dpad, &P.groups, &P.chunks_per_group);
+    const size_t dp = e->dpad;
+    int rc;
+    if ((rc = dev_alloc(e, &P.n, 1)) != LMC_OK) return rc;
+    if ((rc = dev_alloc(e, &P.shift, dp)) != LMC_OK) return rc;
+    if ((rc = dev_alloc(e, &P.s, dp)) != LMC_OK) return rc;
+    if ((rc = dev_alloc(e, &P.S, dp * dp)) != LMC_OK) return rc;
+    if ((rc = dev_alloc(e, &P.part, static_cast<size_t>(P.groups) * pool_tiles(P.dpad) * 256, false)) != LMC_OK) return rc;
+    if ((rc = dev_alloc(e, &P.spart, static_cast<size_t>(P.groups) * dp, false)) != LMC_OK) return rc;
+    e->pool_ready = true;
+    e->pool_shifted = false;
+    return LMC_OK;
+}
+
+int lmc_engine_pool_reset(lmc_engine* e) {
+    const int rc = pool_ensure(e);
+    if (rc != LMC_OK) return rc;
+    const size_t dp = e->dpad;
+    hipStream_t st = main_stream(e);
+    HIP_TRY(e, hipMemsetAsync(e->pool.n, 0, sizeof(long long), st));
+    HIP_TRY(e, hipMemsetAsync(e->pool.shift, 0, dp * sizeof(double), st));
+    HIP_TRY(e, hipMemsetAsync(e->pool.s, 0, dp * sizeof(double), st));
+    HIP_TRY(e, hipMemsetAsync(e->pool.S, 0, dp * dp * sizeof(double), st));
+    e->pool_shifted = false;
+    return LMC_OK;
+}
+
+// Enqueued on the main stream: main_stream() orders it after every sub-block launch in flight, and the next lmc_engine_run()
+// orders its sub-block streams after the main stream (order_sub_blocks_after_main) before it overwrites q.
+int lmc_engine_pool_accumulate(lmc_engine* e) {
+    int rc = pool_ensure(e);
+    if (rc != LMC_OK) return rc;
+    if (e->cfg.chains < 2) return fail(e, LMC_ERR_INVALID, "a covariance pooled across chains needs at least 2 chains");
+    hipStream_t st = main_stream(e);
+    if (!e->pool_shifted) {
+        rc = pool_launch_shift(st, e->pool, e->A.q, e->cfg.chains);
+        if (rc != 0) return launched(e, rc);
+        e->pool_shifted = true;
+    }
+    return launched(e, pool_launch_accumulate(st, e->pool, e->A.q, e->cfg.chains));
+}
+
+// n, mean [dim], m2 [dim][dim] (symmetric) of the statistic as the device holds it; synchronises
+static int pool_fetch(lmc_engine* e, long long* n_out, std::vector<double>& mean, std::vector<double>& m2) {
+    const int rc = pool_ensure(e);
+    if (rc != LMC_OK) return rc;
+    const int d = e->cfg.dim, dp = e->dpad;
+    HIP_TRY(e, hipStreamSynchronize(main_stream(e)));
+    long long n = 0;
+    std::vector<double> shift(dp), s(dp), S(static_cast<size_t>(dp) * dp);
+    HIP_TRY(e, hipMemcpy(&n, e->pool.n, sizeof(n), hipMemcpyDeviceToHost));
+    HIP_TRY(e, hipMemcpy(shift.data(), e->pool.shift, shift.size() * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(e, hipMemcpy(s.data(), e->pool.s, s.size() * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(e, hipMemcpy(S.data(), e->pool.S, S.size() * sizeof(double), hipMemcpyDeviceToHost));
+    *n_out = n;
+    mean.assign(d, 0.0);
+    m2.assign(static_cast<size_t>(d) * d, 0.0);
+    if (n < 1) return LMC_OK;
+    const long double nn = static_cast<long double>(n);
+    for (int i = 0; i < d; ++i) {
+        mean[i] = static_cast<double>(static_cast<long double>(shift[i]) + static_cast<long double>(s[i]) / nn);
+        for (int j = 0; j <= i; ++j) {   // the device keeps the lower triangle
+            const long double v = static_cast<long double>(S[static_cast<size_t>(i) * dp + j]) -
+                                  static_cast<long double>(s[i]) * static_cast<long double>(s[j]) / nn;
+            m2[static_cast<size_t>(i) * d + j] = m2[static_cast<size_t>(j) * d + i] = static_cast<double>(v);
+        }
+    }
+    return LMC_OK;
+}
+
+int lmc_engine_pool_get(lmc_engine* e, int64_t* n, double* mean, double* m2) {
+    long long nn = 0;
+    std::vector<double> mean_h, m2_h;
+    const int rc = pool_fetch(e, &nn, mean_h, m2_h);
+    if (rc != LMC_OK) return rc;
+    if (n) *n = nn;
+    if (mean) HIP_TRY(e, hipMemcpy(mean, mean_h.data(), mean_h.size() * sizeof(double), hipMemcpyDefault));
+    if (m2) HIP_TRY(e, hipMemcpy(m2, m2_h.data(), m2_h.size() * sizeof(double), hipMemcpyDefault));
+    return LMC_OK;
+}
+
+// cov = m2 / (n - 1), Stan's shrinkage towards 1e-3 I with the weight of five samples, then install_full(): the installed
+// matrix stays as it is unless the estimate is finite and factorises
+int lmc_engine_pool_apply(lmc_engine* e) {
+    long long n = 0;
+    std::vector<double> mean, cov;
+    const int rc = pool_fetch(e, &n, mean, cov);
+    if (rc != LMC_OK) return rc;
+    if (n < 2) return fail(e, LMC_ERR_INVALID, "a pooled covariance needs at least 2 samples (got %lld)", n);
+    const int d = e->cfg.dim;
+    const double nn = static_cast<double>(n);
+    const double keep = nn / (nn + 5.0), ridge = 1e-3 * (5.0 / (nn + 5.0));
+    for (int i = 0; i < d; ++i)
+        for (int j = 0; j < d; ++j) {
+            double c = cov[static_cast<size_t>(i) * d + j] / (nn - 1.0);
+            c = keep * c;
+            if (i == j) c = c + ridge;
+            if (!std::isfinite(c)) return fail(e, LMC_ERR_INVALID, "the pooled covariance is not finite");
+            cov[static_cast<size_t>(i) * d + j] = c;
+        }
+    return install_full(e, cov);
+}
+
+int lmc_engine_restart_dual_average(lmc_engine* e) {
+    const int rc = pool_check(e);
+    if (rc != LMC_OK) return rc;
+    return launched(e, pool_launch_restart_da(main_stream(e), e->A.da, e->A.da_count, e->cfg.chains));
 }
 
 static int dense_state_xfer(lmc_engine* e, const lmc_dense_state* st, bool to_user) {

@@ -687,6 +687,31 @@ class Engine:
         """potential.update(current position, grad, tune) for every chain (quadpotential.py:528-552)."""
         self._check(self._lib.lmc_engine_dense_update(self._h, int(bool(tune))))
 
+    # ---- one shared dense matrix adapted from all chains (QuadPotentialFullPooled) -------------------
+    def pool_reset(self):
+        """Zero the pooled second-moment statistic (lmc_engine_pool_reset)."""
+        self._check(self._lib.lmc_engine_pool_reset(self._h))
+
+    def pool_accumulate(self):
+        """Add the current position of every chain to the statistic: enqueued behind the launches so far, no host wait."""
+        self._check(self._lib.lmc_engine_pool_accumulate(self._h))
+
+    def pool_get(self):
+        """(n, mean [dim], m2 [dim, dim]) of the statistic; synchronises."""
+        n = C.c_int64()
+        mean = np.empty(self.dim)
+        m2 = np.empty((self.dim, self.dim))
+        self._check(self._lib.lmc_engine_pool_get(self._h, C.byref(n), _abi.ptr(mean), _abi.ptr(m2)))
+        return int(n.value), mean, m2
+
+    def pool_apply(self):
+        """Install the shrunk pooled covariance as the engine's shared matrix (lmc_engine_pool_apply); synchronises."""
+        self._check(self._lib.lmc_engine_pool_apply(self._h))
+
+    def restart_dual_average(self):
+        """Stan's restart of step-size adaptation after a change of metric, per chain (lmc_engine_restart_dual_average)."""
+        self._check(self._lib.lmc_engine_restart_dual_average(self._h))
+
     def keep_moments(self, enable=True):
         """Accumulate per-chain mean / M2 of the post-warm-up draws on the device (no trace needed for R-hat)."""
         self._check(self._lib.lmc_engine_keep_moments(self._h, int(bool(enable))))

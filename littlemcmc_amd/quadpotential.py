@@ -326,6 +326,48 @@ class QuadPotentialFull(_DensePotential):
     __call__ = QuadPotential.random
 
 
+MAX_DENSE_POOLED_NDIM = 256  # QuadPotentialFullPooled: the fused dense shapes (the statistic is formed by csrc/lmc_pool.hip)
+SNAPSHOTS_PER_WINDOW = 8     # launches an adaptation window of a pooled job is cut into: one snapshot of all chains after each
+
+
+class QuadPotentialFullPooled(QuadPotentialFull):
+    """One float32 covariance shared by all chains, adapted during tuning from the positions of ALL chains of the job
+    (no counterpart in the reference, whose adaptive dense potential learns one matrix per chain from that chain's own
+    draws): with C chains one iteration holds C draws of the target. ``sample()`` runs Stan's windowed warm-up
+    (``sampling.pooled_windows(tune)``: initial buffer, doubling windows, final buffer); every window is cut into
+    ``SNAPSHOTS_PER_WINDOW`` launches, after each of which the device adds the current position of every chain to a
+    second-moment statistic (csrc/lmc_pool.hip, on the matrix cores); at a window's end the shrunk covariance
+    ``n/(n+5) cov + 1e-3 * 5/(n+5) I`` becomes the matrix of all chains, step-size adaptation restarts and the statistic
+    is cleared. The draws run in the kernels of ``QuadPotentialFull``. The schedule is fixed: there are no options but
+    the starting matrix (identity by default). After ``sample()``, ``_cov`` / ``_chol`` hold the adapted matrix.
+
+    * ``update()`` is the inherited no-op: a one-chain ``_astep`` has nothing to pool.
+    * The chains of a pooled job are coupled through the matrix, so -- unlike every other job of this engine -- they
+      are NOT prefix-stable in the chain count: chain k of a 1 000-chain job is not chain k of a 2 000-chain job.
+      The same seeds and the same chain count give the same arrays bit for bit (the statistic is summed in an order
+      that depends on the chain count alone, without floating-point atomics).
+    * ``chains * 8 <= model_ndim`` is refused (the estimate would be singular but for the shrinkage); one GPU per job."""
+
+    _pooled = True
+
+    def __init__(self, n, initial_cov=None):
+        n = int(n)
+        if n > MAX_DENSE_POOLED_NDIM:
+            raise NotImplementedError("pooled dense mass matrices run on the device up to model_ndim = %d" % MAX_DENSE_POOLED_NDIM)
+        if initial_cov is None:
+            initial_cov = np.eye(n)
+        initial_cov = np.asarray(initial_cov)
+        if initial_cov.shape != (n, n):
+            raise ValueError("Wrong shape for initial_cov: expected %s got %s" % ((n, n), initial_cov.shape))
+        super().__init__(initial_cov)
+
+    def check_chains(self, chains):
+        """A job of ``chains`` chains can estimate an n x n covariance from one snapshot only with chains * 8 > n."""
+        if int(chains) * 8 <= self._n:
+            raise ValueError("a covariance pooled across chains needs chains * 8 > model_ndim (got %d chains, model_ndim = %d)"
+                             % (chains, self._n))
+
+
 class QuadPotentialFullInv(_DensePotential):
     """quadpotential.py:388-425: mass matrix ``A`` (inverse covariance); velocity = A^-1 x, momentum = L z."""
 

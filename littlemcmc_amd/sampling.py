@@ -17,7 +17,7 @@ import numpy as np
 from . import _abi
 from .base_hmc import raise_for_status
 from .nuts import NUTS
-from .quadpotential import QuadPotentialDiagAdapt, QuadPotentialFullAdapt
+from .quadpotential import SNAPSHOTS_PER_WINDOW, QuadPotentialDiagAdapt, QuadPotentialFullAdapt, QuadPotentialFullPooled
 from .targets import require_device_target
 
 _log = logging.getLogger("littlemcmc_amd")
@@ -40,7 +40,9 @@ def _derive_seeds(random_seed, chains):
 
 def init_nuts(logp_dlogp_func, model_ndim=None, init="auto", random_seed=None, size=None, **kwargs):
     """Set up start point and NUTS sampler (sampling.py:524-605): "adapt_diag", "jitter+adapt_diag",
-    "adapt_full", "jitter+adapt_full" (dense modes: model_ndim <= 256)."""
+    "adapt_full", "jitter+adapt_full" (dense modes: model_ndim <= 256), and "adapt_full_pooled" / "jitter+adapt_full_pooled":
+    start points as the adapt_full pair, one dense matrix shared by all chains and adapted from all of them
+    (QuadPotentialFullPooled; no counterpart in the reference)."""
     if model_ndim is None:
         model_ndim = size if size is not None else getattr(logp_dlogp_func, "d", None)
     logp_dlogp_func = require_device_target(logp_dlogp_func, model_ndim)
@@ -59,11 +61,15 @@ def init_nuts(logp_dlogp_func, model_ndim=None, init="auto", random_seed=None, s
         start = 2 * np.random.rand(model_ndim) - 1
     elif init == "adapt_full":
         start = np.zeros(model_ndim)
-    elif init == "jitter+adapt_full":
+    elif init in ("jitter+adapt_full", "jitter+adapt_full_pooled"):
         start = 2 * np.random.rand(model_ndim) - 1
+    elif init == "adapt_full_pooled":
+        start = np.zeros(model_ndim)
     else:
         raise ValueError("Unknown initializer: {}.".format(init))
-    if init.endswith("adapt_full"):   # sampling.py:588-597
+    if init.endswith("adapt_full_pooled"):
+        potential = QuadPotentialFullPooled(model_ndim)
+    elif init.endswith("adapt_full"):   # sampling.py:588-597
         potential = QuadPotentialFullAdapt(model_ndim, start, np.eye(model_ndim), 10)
     else:
         potential = QuadPotentialDiagAdapt(model_ndim, start, np.ones(model_ndim), 10)
@@ -174,7 +180,8 @@ class _ResultStreamer:
         return self.out
 
 
-def _run_job(eng, tune, n_total, per_launch, progressbar, callback=None, on_enqueued=None, before_enqueue=None):
+def _run_job(eng, tune, n_total, per_launch, progressbar, callback=None, on_enqueued=None, before_enqueue=None,
+             first_iter=0, job_total=None):
     """Enqueue the job's launches, then wait for them in a way Ctrl-C can reach (sampling.py:324-328, :470-471 in the
     reference: a KeyboardInterrupt ends sampling and what has been drawn so far is returned).
 
@@ -186,7 +193,9 @@ def _run_job(eng, tune, n_total, per_launch, progressbar, callback=None, on_enqu
     every launch is enqueued on all devices before anything is waited for, and a launch counts as complete when it is
     complete everywhere. ``on_enqueued(first, n)`` is called right after the launch of iterations [first, first + n) has
     been enqueued (sample() enqueues the copy of that window into the result arrays there, so the copy of launch k runs under
-    launch k + 1); ``before_enqueue(first, n)`` right before it is. Returns (iterations completed by EVERY chain, interrupted)."""
+    launch k + 1); ``before_enqueue(first, n)`` right before it is. ``first_iter`` > 0: the iterations [first_iter, n_total)
+    of a job whose earlier iterations have run (a job driven in segments: _run_job_pooled); ``job_total`` is then the
+    length of the whole job, which progress is reported against. Returns (iterations completed by EVERY chain, interrupted)."""
     import time
 
     engines = getattr(eng, "engines", [eng])
@@ -209,7 +218,8 @@ def _run_job(eng, tune, n_total, per_launch, progressbar, callback=None, on_enqu
     if not sizes or min(sizes) < 1:
         raise ValueError("launch sizes must be >= 1 iteration (got %r)" % (per_launch,))
     pending = []
-    it = 0
+    it = int(first_iter)
+    job_total = n_total if job_total is None else int(job_total)
     while it < n_total:
         n = min(sizes[min(len(pending), len(sizes) - 1)], n_total - it)
         pending.append((it, n))
@@ -248,7 +258,7 @@ def _run_job(eng, tune, n_total, per_launch, progressbar, callback=None, on_enqu
                     at = eng.progress()
                     if at != seen:
                         seen = at
-                        callback(trace=None, draw=JobProgress(at, n_total, at < tune, eng.chains, launches_done))
+                        callback(trace=None, draw=JobProgress(at, job_total, at < tune, eng.chains, launches_done))
                 if all(e_.query() for e_ in marks[0][1]):
                     done = marks.pop(0)[0]
                     launches_done += 1
@@ -257,13 +267,13 @@ def _run_job(eng, tune, n_total, per_launch, progressbar, callback=None, on_enqu
                     if progressbar and done != reported:
                         reported = done
                         _log.info("Sampling %d chains: %d/%d iterations (%s), %.1f s" % (
-                            eng.chains, done, n_total, "tuning" if done <= tune else "drawing", time.perf_counter() - t0))
+                            eng.chains, done, job_total, "tuning" if done <= tune else "drawing", time.perf_counter() - t0))
                     continue
                 time.sleep(0.0005)
             eng.synchronize()
         return n_total, False
     except KeyboardInterrupt:
-        return _interrupted(eng, n_total, stop_device=eng.target.family != _abi.TARGET_EXTERNAL)
+        return _interrupted(eng, job_total, stop_device=eng.target.family != _abi.TARGET_EXTERNAL)
 
 
 def _interrupted(eng, n_total, stop_device):
@@ -310,6 +320,72 @@ def _run_job_host_step_rand(eng, step, tune, n_total, progressbar, callback=None
             eng.set_step_sizes(None)
         except Exception as cleanup_err:
             _log.warning("cleanup after the per-iteration job failed: %s" % cleanup_err)
+
+
+def pooled_windows(tune):
+    """Adaptation windows [(begin, end), ...] of a pooled dense mass matrix over ``tune`` tuning iterations: Stan's
+    warm-up layout. Nothing for tune < 20. Initial buffer 75, final buffer 50, first window 25 -- or, where
+    75 + 25 + 50 > tune, int(0.15 tune), int(0.1 tune) and one window between. Windows double; a window whose successor
+    would not fit before the final buffer is stretched to it."""
+    tune = int(tune)
+    if tune < 20:
+        return []
+    init_buffer, term_buffer, window = 75, 50, 25
+    if init_buffer + window + term_buffer > tune:
+        init_buffer, term_buffer = int(0.15 * tune), int(0.1 * tune)
+        window = tune - init_buffer - term_buffer
+    last = tune - term_buffer
+    out, begin = [], init_buffer
+    while begin < last:
+        end = begin + window
+        if end + 2 * window > last:
+            end = last
+        out.append((begin, end))
+        begin, window = end, 2 * window
+    return out
+
+
+def _snapshot_launches(begin, end):
+    """The launches an adaptation window [begin, end) is cut into: SNAPSHOTS_PER_WINDOW of equal length, the last takes the
+    remainder; one per iteration where the window is shorter than that."""
+    k = min(SNAPSHOTS_PER_WINDOW, end - begin)
+    each = (end - begin) // k
+    return [each] * (k - 1) + [end - begin - each * (k - 1)]
+
+
+def _run_job_pooled(eng, tune, n_total, per_launch, progressbar, callback=None, on_enqueued=None, before_enqueue=None):
+    """The job loop of QuadPotentialFullPooled. Inside every window of pooled_windows(tune) the launches are those of
+    _snapshot_launches() and each is followed by a snapshot of all chains (Engine.pool_accumulate: enqueued behind the
+    launch, no host wait); at a window's end the pooled covariance becomes the matrix of all chains, step-size adaptation
+    restarts and the statistic is cleared (memoryless windows). Only the window ends drain the device. Everything outside
+    the windows runs as in any other job; every segment goes through _run_job, so callback, progress, Ctrl-C and the
+    result streamer's hooks see every launch. Returns what _run_job returns."""
+    def after_snapshot_launch(first, n):
+        eng.pool_accumulate()
+        if on_enqueued is not None:
+            on_enqueued(first, n)
+
+    def segment(first, last, sizes, hook):
+        return _run_job(eng, tune, last, sizes, progressbar, callback, on_enqueued=hook, before_enqueue=before_enqueue,
+                        first_iter=first, job_total=n_total)
+
+    at = 0
+    eng.pool_reset()
+    for begin, end in pooled_windows(tune):
+        if begin > at:
+            n_done, interrupted = segment(at, begin, per_launch, on_enqueued)
+            if interrupted:
+                return n_done, True
+        n_done, interrupted = segment(begin, end, _snapshot_launches(begin, end), after_snapshot_launch)
+        if interrupted:
+            return n_done, True
+        eng.pool_apply()
+        eng.restart_dual_average()
+        eng.pool_reset()
+        at = end
+    if at < n_total:
+        return segment(at, n_total, per_launch, on_enqueued)
+    return n_total, False
 
 
 def visible_devices():
@@ -526,7 +602,17 @@ def sample(logp_dlogp_func, model_ndim=None, draws=1000, tune=1000, step=None, i
         finally:
             probe.close()
 
+    pooled = getattr(step.potential, "_pooled", False)
+    if pooled:   # one matrix from the positions of all chains (QuadPotentialFullPooled): one GPU, enough chains, device iterations
+        step.potential.check_chains(chains)
+        if external or getattr(step, "_host_step_rand", lambda: None)() is not None:
+            raise NotImplementedError("a pooled dense mass matrix needs a device density and a device step_rand (the job "
+                                      "runs in launches of many iterations)")
+        if devices is None and device is None:
+            gpu_cap = 1          # no automatic fan-out over the visible GPUs
     devs = _resolve_devices(devices, device, gpu_cap, chains, _probe_slots)
+    if pooled and len(devs) > 1:
+        raise NotImplementedError("a pooled dense mass matrix is adapted on one GPU (got devices=%r)" % (devs,))
     eng = _make_engines(step, chains, devs)
     try:
         eng.seed(seeds)                       # np.random.seed(random_seed[i]) per chain (sampling.py:496-497)
@@ -551,7 +637,8 @@ def sample(logp_dlogp_func, model_ndim=None, draws=1000, tune=1000, step=None, i
             if host_rand:
                 n_done, interrupted = _run_job_host_step_rand(eng, step, tune, n_total, progressbar, callback)
             else:
-                n_done, interrupted = _run_job(eng, tune, n_total, per_launch, progressbar, callback,
+                n_done, interrupted = (_run_job_pooled if pooled else _run_job)(
+                                               eng, tune, n_total, per_launch, progressbar, callback,
                                                on_enqueued=streamer.window if streamer is not None else None,
                                                before_enqueue=streamer.before_launch if streamer is not None else None)
         except BaseException:
