@@ -78,9 +78,22 @@ extern "C" {
  * (iteration, element), float32 Box-Muller: the throughput mode for callers that do not need the reference's draws
  * (the momentum draw is ~20 % of a depth-3 iteration on the parity stream). Tree uniforms stay on MT19937 in both.
  * Fused diagonal-mass kernels with the built-in densities (in a team of wavefronts every thread draws its own
- * elements: the draw needs no barrier, where the parity stream is produced by wave 0 alone). */
+ * elements: the draw needs no barrier, where the parity stream is produced by wave 0 alone).
+ * COUNTER: PHILOX's momentum draw, and every uniform of the transition -- the device step jitter's, the tree's directions
+ * and merges, HMC's path length and acceptance -- from a second counter-based stream: u_k, the k-th uniform iteration
+ * `git` of a chain consumes (k from 0 in the sequential algorithm's order), is
+ *   w = philox4x32_10(c0 = (uint32)git, c1 = (uint32)(git >> 32), c2 = k >> 1, c3 = 0x6c6d6375 "lmcu", k0 = seed, k1 = 0x4d4f4d31)
+ *   (a, b) = (w[0], w[1]) for even k, (w[2], w[3]) for odd k;   u_k = ((a >> 5) * 2^26 + (b >> 6)) / 2^53   in [0, 1)
+ * (the momentum stream counts (git, thread) under c3 = 0x6c6d636d "lmcm": disjoint counter spaces). What iteration t of a
+ * chain does is then a pure function of (seed, t, the chain's state): no generator state exists -- the chain's MT19937
+ * arrays are neither read nor written, the kernels reserve no LDS for them -- results do not depend on launch slicing or
+ * on the chain-block partition, and lmc_engine_counter_draws() hands out the very numbers, so that a host model replays
+ * any iteration. Fused diagonal-mass kernels with the built-in densities AND run-time compiled user densities
+ * (LMC_TARGET_USER); refused (LMC_ERR_INVALID) with dense mass matrices, in the general kernels and with
+ * LMC_TARGET_EXTERNAL. Not same-seed comparable with the reference, nor with PHILOX. */
 #define LMC_RNG_NUMPY 0
 #define LMC_RNG_PHILOX 1
+#define LMC_RNG_COUNTER 2
 
 /* LDS plan of the one-wave fused sampling kernels (csrc/lmc_sampler.hpp: PairLds<NS, 1, PL>). SHALLOW keeps the chain's
  * MT19937 state and the cold slots of the trajectory in LDS and subtree-stack level 1; DEEP uses the generator in place
@@ -193,7 +206,7 @@ typedef struct lmc_config {
  * (quadpotential.py:388-468), QuadPotentialFullAdapt up to dim 1024 (:470-560; the refresh then factorises through HBM),
  * QuadPotentialDiagAdapt / QuadPotentialFullAdapt(dtype="float64") -- runs in the GENERAL kernels (csrc/lmc_wide.hpp: one
  * chain = one wavefront up to dim 512, a workgroup of 16 wavefronts beyond, the tree in the chain's HBM row): the same
- * algorithm, statement for statement, several times slower per leapfrog. Not in the general kernels: LMC_RNG_PHILOX, and LMC_TARGET_EXTERNAL with
+ * algorithm, statement for statement, several times slower per leapfrog. Not in the general kernels: LMC_RNG_PHILOX / LMC_RNG_COUNTER, and LMC_TARGET_EXTERNAL with
  * anything but a float32 diagonal. A shared matrix adapted from all chains (lmc_engine_pool_*, LMC_POT_FULL up to dim 256) samples
  * in the LMC_POT_FULL kernels; its statistic is formed by pool_accumulate_kernel (csrc/lmc_pool.hip) on the matrix cores. */
 /* Fill *cfg with the reference's defaults for the given shape. */
@@ -518,6 +531,11 @@ int lmc_engine_logp_dlogp(lmc_engine* e, const double* q, double* logp, double* 
 int lmc_engine_rng_draw(lmc_engine* e, const int32_t* ops, int32_t n_ops, double* out);
 /* potential.random() for every chain (quadpotential.py:221-224 / :374-376): out [chains][dim]. */
 int lmc_engine_draw_momentum(lmc_engine* e, double* out);
+/* What the counter-based streams hand iteration `iteration` of every chain (a pure function of lmc_engine_seed's seeds):
+ * normals  [chains][dim]: the standard normals of the momentum draw, before the mass scaling (NULL: not wanted)
+ * uniforms [chains][n_uniforms]: the first n_uniforms decision uniforms in consumption order (NULL: not wanted)
+ * LMC_ERR_INVALID on the numpy stream. */
+int lmc_engine_counter_draws(lmc_engine* e, int64_t iteration, double* normals, double* uniforms, int32_t n_uniforms);
 
 /* ---- a user-written density compiled at run time (cfg.target_family = LMC_TARGET_USER in the stock library) ------------
  * The kernels that depend on the density functor -- run_kernel<run_ns, run_w, UserTarget>, trajectory_kernel<unit_ns,

@@ -19,7 +19,7 @@ POT_DIAG_ADAPT, POT_DIAG, POT_FULL, POT_FULL_INV, POT_FULL_ADAPT, POT_FULL_F64 =
 TARGET_STD_NORMAL, TARGET_DIAG_GAUSSIAN, TARGET_AR1, TARGET_FUNNEL, TARGET_NORMAL1D, TARGET_USER, TARGET_EXTERNAL = range(7)
 STATUS_BAD_INITIAL_ENERGY = 1
 SDOT_NATIVE, SDOT_OPENBLAS_SKYLAKEX, SDOT_OPENBLAS_HASWELL = 0, 1, 2
-RNG_NUMPY, RNG_PHILOX = 0, 1
+RNG_NUMPY, RNG_PHILOX, RNG_COUNTER = 0, 1, 2
 LDS_PLAN_AUTO, LDS_PLAN_SHALLOW, LDS_PLAN_DEEP = 0, 1, 2
 PLANE_F64, PLANE_I32, PLANE_U8 = 0, 1, 2
 AS_NATIVE, AS_F64, AS_I64 = 0, 1, 2
@@ -172,6 +172,7 @@ _SIGNATURES = {
     "lmc_engine_logp_dlogp": (C.c_int, [_P, _P, _P, _P]),
     "lmc_engine_rng_draw": (C.c_int, [_P, _P, C.c_int32, _P]),
     "lmc_engine_draw_momentum": (C.c_int, [_P, _P]),
+    "lmc_engine_counter_draws": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int32]),
     "lmc_engine_kernel_shape": (C.c_int, [_P, _P, _P, _P]),
     "lmc_engine_uses_general_kernels": (C.c_int32, [_P]),
     "lmc_engine_occupancy": (C.c_int, [_P, _P, _P, _P]),

@@ -67,6 +67,14 @@ class StepRandUniform:
         return "StepRandUniform(%r, %r)" % (self.lo, self.hi)
 
 
+def check_rng(rng):
+    """``rng=`` of the steps: "numpy" (the reference's stream, the default) or "counter" (every random number of a
+    transition from the counter-based streams, include/lmc_hip.h: LMC_RNG_COUNTER)."""
+    if rng not in ("numpy", "counter"):
+        raise ValueError("rng must be 'numpy' or 'counter' (got %r)" % (rng,))
+    return rng
+
+
 class BaseHMC:
     """Superclass of the Hamiltonian samplers (base_hmc.py:29)."""
 
@@ -112,7 +120,8 @@ class BaseHMC:
             gamma=self._gamma, k=self._k, t0=self._t0,
             adaptation_window=getattr(self.potential, "_initial_adaptation_window", 101),
             adaptation_window_multiplier=getattr(self.potential, "adaptation_window_multiplier", 1.0),
-            rng=getattr(self, "_momentum_rng", "numpy"),
+            # rng="counter" implies the Philox momentum draw; left alone, momentum_rng keeps its meaning
+            rng="counter" if getattr(self, "_rng", "numpy") == "counter" else getattr(self, "_momentum_rng", "numpy"),
             mass_dtype=getattr(self.potential, "dtype", "float32") if self.potential._engine_kind in ("diag_adapt", "diag", "full_adapt") else "float32",
         )
 

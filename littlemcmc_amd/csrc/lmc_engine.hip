@@ -101,6 +101,32 @@ __global__ __launch_bounds__(64) void momentum_kernel(ChainArrays A, int momentu
     }
 }
 
+// lmc_engine_counter_draws: what the counter-based streams hand iteration `git` -- the momentum normals through the very
+// call the sampling kernel of shape (NS, 64 * W threads) makes, the uniforms through the stream's own window (counter_next)
+template <int NS>
+__global__ void counter_draws_kernel(ChainArrays A, long long git, double* normals, double* uniforms, int n_uniforms) {
+    const int c = blockIdx.x, tid = threadIdx.x, d = A.d;
+    const uint32_t seed = first_u32(A.seed[c]);
+    if (normals != nullptr) {
+        double z[NS];
+        philox_normals<NS>(seed, git, tid, d, z);
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            const int e = tid * NS + s;
+            if (e < d) normals[static_cast<long long>(c) * d + e] = z[s];
+        }
+    }
+    if (uniforms != nullptr && tid < 64) {   // wave 0 (every wave of a team would hand out the same values)
+        CounterStream r;
+        r.seed = seed;
+        counter_begin(r, git);
+        for (int k = 0; k < n_uniforms; ++k) {
+            const double u = counter_next(r);
+            if (tid == 0) uniforms[static_cast<long long>(c) * n_uniforms + k] = u;
+        }
+    }
+}
+
 // QuadPotentialDiagAdapt.reset() (quadpotential.py:195-204) / QuadPotentialDiag.__init__ (:349-365)
 // + DualAverageAdaptation.reset() (step_sizes.py:49-56) + iter_count = 0.
 __global__ void reset_kernel(ChainArrays A, const double* init_mean, const float* init_diag, const double* init_diag64,
@@ -566,8 +592,12 @@ static int relay_mask_for(long long n) {
 // a density compiled at run time (hiprtc): its kernels are a module's (user_launch), not this library's
 static bool rtc_user(int family) { return family == LMC_TARGET_USER && !kUserCompiledIn; }
 // dynamic LDS of a sampling-kernel workgroup under plan 0 (stack + tail: MT19937, team exchange) / plan 1 (stack only)
+// (LMC_RNG_COUNTER: its one layout is the engine's "plan 0" -- e->lds_bytes -- and no generator follows the stack)
+static int sampling_tail_doubles(const lmc_config& cfg, int run_w) {
+    return cfg.rng_mode == LMC_RNG_COUNTER ? lds_tail_doubles_counter(run_w) : lds_tail_doubles(run_w);
+}
 static int sampling_lds_bytes(const lmc_engine* e, int plan = 0) {
-    return plan == 1 ? e->lds_bytes1 : e->lds_bytes + lds_tail_doubles(e->run_w) * 8;
+    return plan == 1 ? e->lds_bytes1 : e->lds_bytes + sampling_tail_doubles(e->cfg, e->run_w) * 8;
 }
 // Which LDS plan the launches enqueued NOW run under (lmc_sampler.hpp: run_kernel<.., PL>; results do not depend on it). Relay
 // chains leave their own mean tree size of the running launch in a pinned host word as they go (stop_request_load), so
@@ -681,6 +711,7 @@ typedef void (*RunKernel)(ChainArrays, SamplerParams, const double*);
 template <int NS, int W, template <int> class T>
 static RunKernel run_kernel_of_shape(const lmc_engine* e, int plan) {
     if (e->cfg.rng_mode == LMC_RNG_PHILOX) return &run_kernel<NS, W, T, 1>;
+    if (e->cfg.rng_mode == LMC_RNG_COUNTER) return &run_kernel<NS, W, T, 2>;
     if constexpr (W == 1) {
         const bool pinned_pairs = e->leaf_group != run_leaf_group(NS, 1);
         if (plan == 1) return pinned_pairs ? &run_kernel<NS, 1, T, 0, 1, 2> : &run_kernel<NS, 1, T, 0, 1>;
@@ -825,7 +856,8 @@ int lmc_engine_create(const lmc_config* cfg, lmc_engine** out) {
             return fail(nullptr, LMC_ERR_INVALID, "an externally evaluated density runs with diagonal float32 mass matrices at any dim up to %d, "
                                                   "with dense ones up to dim 256; give the density as a device functor for the other shapes", kWideMaxDim);
         if (cfg->rng_mode != LMC_RNG_NUMPY)
-            return fail(nullptr, LMC_ERR_INVALID, "LMC_RNG_PHILOX runs in the fused kernels only");
+            return fail(nullptr, LMC_ERR_INVALID, "%s runs in the fused kernels only",
+                        cfg->rng_mode == LMC_RNG_COUNTER ? "LMC_RNG_COUNTER" : "LMC_RNG_PHILOX");
     }
     if (!lmc_has_target(cfg->target_family))
         return fail(nullptr, LMC_ERR_INVALID, "target family %d is not built into this library", cfg->target_family);
@@ -837,8 +869,12 @@ int lmc_engine_create(const lmc_config* cfg, lmc_engine** out) {
         return fail(nullptr, LMC_ERR_INVALID, "unknown start_energy_sdot mode %d", cfg->start_energy_sdot);
     if (cfg->adaptation_window < 1 || !(cfg->adaptation_window_multiplier > 0.0))
         return fail(nullptr, LMC_ERR_INVALID, "adaptation_window must be >= 1 and its multiplier > 0");
-    if (cfg->rng_mode != LMC_RNG_NUMPY && cfg->rng_mode != LMC_RNG_PHILOX)
+    if (cfg->rng_mode != LMC_RNG_NUMPY && cfg->rng_mode != LMC_RNG_PHILOX && cfg->rng_mode != LMC_RNG_COUNTER)
         return fail(nullptr, LMC_ERR_INVALID, "unknown rng_mode %d", cfg->rng_mode);
+    // (a user density is welcome in this mode: its run-time compiled kernel is run_kernel<NS, W, UserTarget, 2>)
+    if (cfg->rng_mode == LMC_RNG_COUNTER && (cfg->potential >= LMC_POT_FULL || cfg->target_family == LMC_TARGET_EXTERNAL))
+        return fail(nullptr, LMC_ERR_INVALID, "LMC_RNG_COUNTER runs in the fused diagonal-mass kernels with a device density "
+                                              "(no dense mass matrix, no externally evaluated density)");
     if (cfg->rng_mode == LMC_RNG_PHILOX && (cfg->potential >= LMC_POT_FULL ||
                                             cfg->target_family == LMC_TARGET_USER || cfg->target_family == LMC_TARGET_EXTERNAL))
         return fail(nullptr, LMC_ERR_INVALID, "LMC_RNG_PHILOX runs in the fused diagonal-mass kernels with the built-in densities");
@@ -938,7 +974,7 @@ int lmc_engine_create(const lmc_config* cfg, lmc_engine** out) {
     e->leaf_group = (!wide && run_leaf_group(e->run_ns, e->run_w) == 4 && cfg->tuning.leaf_group != 2) ? 4 : 2;
     // kernels only, and the counter-based momentum stream its own default instantiation (the LDS sizes below must be those of
     // the kernel that runs)
-    if (rtc_user(cfg->target_family) || cfg->rng_mode == LMC_RNG_PHILOX)
+    if (rtc_user(cfg->target_family) || cfg->rng_mode != LMC_RNG_NUMPY)
         e->leaf_group = run_leaf_group(e->run_ns, e->run_w);
     const int lg = e->leaf_group;
     if (wide) {
@@ -947,16 +983,18 @@ int lmc_engine_create(const lmc_config* cfg, lmc_engine** out) {
     } else {
         const int waves_per_cu = 4 * run_waves_per_simd(e->run_ns, e->run_w);
         const int blocks_per_cu = waves_per_cu / e->run_w > 0 ? waves_per_cu / e->run_w : 1;
-        const long budget = (163840L / blocks_per_cu) / 1280 * 1280 - lds_tail_doubles(e->run_w) * 8L;
-        if (pair_min_doubles(e->run_ns, e->run_w, 0, lg) * 8L > budget)
+        const long budget = (163840L / blocks_per_cu) / 1280 * 1280 - sampling_tail_doubles(*cfg, e->run_w) * 8L;
+        // the PairLds plan behind e->lds_bytes: plan 0, or the one layout of the counter mode's kernel (counter_lds_plan)
+        const int lp = cfg->rng_mode == LMC_RNG_COUNTER ? counter_lds_plan(e->run_w) : 0;
+        if (pair_min_doubles(e->run_ns, e->run_w, lp, lg) * 8L > budget)
             return bail(fail(nullptr, LMC_ERR_INVALID, "the sampling kernel's LDS plan does not fit the budget"));
         nlds = cfg->lds_levels > 0 ? cfg->lds_levels : 1;
         if (cfg->lds_levels <= 0)
-            while (nlds < max_levels && pair_total_doubles(e->run_ns, e->run_w, nlds + 1, 0, lg) * 8L <= budget) ++nlds;
+            while (nlds < max_levels && pair_total_doubles(e->run_ns, e->run_w, nlds + 1, lp, lg) * 8L <= budget) ++nlds;
         if (nlds > max_levels) nlds = max_levels;
         if (nlds < 1) nlds = 1;
         e->nlds = nlds;
-        e->lds_bytes = pair_total_doubles(e->run_ns, e->run_w, nlds, 0, lg) * 8;
+        e->lds_bytes = pair_total_doubles(e->run_ns, e->run_w, nlds, lp, lg) * 8;
         // The deep-tree plan of the one-wave kernels (lmc_sampler.hpp: PairLds<NS, 1, 1>, run_kernel's kDynPlan): MT19937 used in
         // place, one cold slot (none at NS = 4) in LDS, and the room that frees holds stack level 2. Same budget per wave (the
         // generator's 2.5 KB included, since it is not in LDS under this plan). By default the engine picks the plan of every
@@ -967,7 +1005,8 @@ int lmc_engine_create(const lmc_config* cfg, lmc_engine** out) {
         e->lds_bytes1 = 0;
         e->lds_plan = 0;
         const long budget1 = (163840L / blocks_per_cu) / 1280 * 1280;
-        if (e->run_w == 1 && run_mt_in_lds(1) && cfg->lds_levels <= 0 && pair_min_doubles(e->run_ns, 1, 1, lg) * 8L <= budget1) {
+        if (e->run_w == 1 && run_mt_in_lds(1) && cfg->lds_levels <= 0 && cfg->rng_mode != LMC_RNG_COUNTER &&
+            pair_min_doubles(e->run_ns, 1, 1, lg) * 8L <= budget1) {
             int n1 = 1;
             while (n1 < max_levels && pair_total_doubles(e->run_ns, 1, n1 + 1, 1, lg) * 8L <= budget1) ++n1;
             e->nlds1 = n1;
@@ -2775,6 +2814,28 @@ int lmc_engine_draw_momentum(lmc_engine* e, double* out) {
         if (rc != LMC_OK) return rc;
     }
     HIP_TRY(e, hipMemcpyAsync(out, dout.p, C * d * sizeof(double), hipMemcpyDefault, main_stream(e)));
+    HIP_TRY(e, hipStreamSynchronize(main_stream(e)));
+    return LMC_OK;
+}
+
+int lmc_engine_counter_draws(lmc_engine* e, int64_t iteration, double* normals, double* uniforms, int32_t n_uniforms) {
+    if (!e) return fail(nullptr, LMC_ERR_INVALID, "null engine");
+    if (e->cfg.rng_mode == LMC_RNG_NUMPY)
+        return fail(e, LMC_ERR_INVALID, "lmc_engine_counter_draws() needs a counter-based stream (LMC_RNG_PHILOX / LMC_RNG_COUNTER), "
+                                        "this engine draws from LMC_RNG_NUMPY");
+    if (iteration < 0 || n_uniforms < 0 || (uniforms && n_uniforms == 0)) return fail(e, LMC_ERR_INVALID, "bad counter_draws arguments");
+    if (!normals && !uniforms) return LMC_OK;
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    const size_t C = e->cfg.chains, d = e->cfg.dim;
+    DevBuf<double> dn, du;
+    if (normals) HIP_TRY(e, dn.alloc(C * d));
+    if (uniforms) HIP_TRY(e, du.alloc(C * static_cast<size_t>(n_uniforms)));
+    const auto kernel = with_int<1, 2, 4>(e->run_ns, [](auto NS) { return &counter_draws_kernel<NS>; });
+    const int rc = launched(e, launch(kernel, dim3(e->cfg.chains), dim3(64 * e->run_w), 0, main_stream(e), e->A,
+                                      static_cast<long long>(iteration), normals ? dn.p : nullptr, uniforms ? du.p : nullptr, n_uniforms));
+    if (rc != LMC_OK) return rc;
+    if (normals) HIP_TRY(e, hipMemcpyAsync(normals, dn.p, C * d * sizeof(double), hipMemcpyDefault, main_stream(e)));
+    if (uniforms) HIP_TRY(e, hipMemcpyAsync(uniforms, du.p, C * n_uniforms * sizeof(double), hipMemcpyDefault, main_stream(e)));
     HIP_TRY(e, hipStreamSynchronize(main_stream(e)));
     return LMC_OK;
 }

@@ -403,7 +403,8 @@ __device__ __forceinline__ void rng_normals_owned(RngState& r, int d, double* ou
 // key = the chain's seed, counter = iteration and lane) and a float32 Box-Muller -- the momentum of QuadPotentialDiagAdapt
 // is float32 in the reference too (quadpotential.py:221-224) -- with the hardware's single-instruction log2 / sin / cos.
 // No LDS, no cross-lane traffic, no barrier; every thread of a team draws its own elements. Results are independent of
-// launch slicing and of the chain-block partition, like the parity stream's. Tree uniforms stay on the chain's MT19937.
+// launch slicing and of the chain-block partition, like the parity stream's. Under LMC_RNG_PHILOX the tree uniforms stay on the
+// chain's MT19937; LMC_RNG_COUNTER takes them from the decision stream below as well.
 struct Philox4 { uint32_t c[4]; };
 __device__ __forceinline__ Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
 #pragma unroll
@@ -439,5 +440,59 @@ __device__ __forceinline__ void philox_normals(uint32_t seed, long long git, int
 #pragma unroll
     for (int s = 0; s < NS; ++s) z[s] = (thread * NS + s < d) ? static_cast<double>(n[s]) : 0.0;
 }
+
+// ---- counter-based decision uniforms (LMC_RNG_COUNTER: every random number of a transition is a pure function) --------
+// u_k, the k-th uniform iteration `git` of the chain seeded `seed` consumes (k counts from 0 in the consumption order of the
+// sequential algorithm: the step jitter's uniform first if the device draws it, then direction, merges, ...):
+//   w = philox4x32_10(c0 = (uint32)git, c1 = (uint32)(git >> 32), c2 = k >> 1, c3 = 0x6c6d6375 "lmcu", k0 = seed, k1 = 0x4d4f4d31)
+//   (a, b) = (w.c[0], w.c[1]) for even k, (w.c[2], w.c[3]) for odd k
+//   u_k = ((a >> 5) * 2^26 + (b >> 6)) / 2^53          rk_double's 53-bit form without the tempering: [0, 1)
+// c3 keeps this counter space disjoint from the momentum stream's ("lmcm"). The same definition is stated in
+// include/lmc_hip.h and restated in Python in tests/_counter_model.py.
+__device__ __forceinline__ double counter_uniform_of(const Philox4& w, int odd) {
+    const uint32_t a = (odd ? w.c[2] : w.c[0]) >> 5;
+    const uint32_t b = (odd ? w.c[3] : w.c[1]) >> 6;
+    return (static_cast<double>(a) * 67108864.0 + static_cast<double>(b)) / 9007199254740992.0;
+}
+// The stream and its look-ahead window in one object: lane l holds u_k for k = wbase + l, so a hand-out is the very
+// v_readlane with a scalar index the MT19937 window uses, and the window costs the same two VGPRs. A refill is one Philox
+// call per lane (the lanes of a pair evaluate the same block and keep one half each; a 128-wide window -- both halves in
+// every lane -- would need a second VGPR pair across the tree build and a select per hand-out, for a refill that is
+// ~100 VALU instructions once per 64 uniforms). Nothing here lives in memory: no state is loaded, stored, twisted or
+// broadcast, and the waves of a team compute identical windows redundantly.
+struct CounterStream {
+    uint32_t seed;
+    uint32_t git_lo, git_hi;   // the iteration whose uniforms are handed out
+    int k;                     // index of the next uniform
+    int wbase;                 // the window holds u_wbase .. u_(wbase + 63); -1: empty
+    double val;
+};
+struct NoWindow {};            // the counter stream carries its own window (rng_window below)
+__device__ __forceinline__ void window_reset(NoWindow&) {}
+__device__ __forceinline__ void counter_begin(CounterStream& r, long long git) {   // iteration `git` starts: k = 0
+    r.git_lo = static_cast<uint32_t>(git);
+    r.git_hi = static_cast<uint32_t>(git >> 32);
+    r.k = 0;
+    r.wbase = -1;
+    r.val = 0.0;
+}
+__device__ inline double counter_next(CounterStream& r) {
+    // wave-uniform control kept scalar (first_i32), as in window_next
+    const int k = first_i32(r.k);
+    const int base = k & ~63;
+    if (base != first_i32(r.wbase)) {
+        const int lane = lane_id();
+        const Philox4 w = philox4x32_10(r.git_lo, r.git_hi, static_cast<uint32_t>((base + lane) >> 1), 0x6c6d6375u /* "lmcu" */,
+                                        r.seed, 0x4d4f4d31u);
+        r.val = counter_uniform_of(w, lane & 1);
+        r.wbase = base;
+    }
+    const double u = readlane_f64(r.val, k & 63);
+    r.k = k + 1;
+    return u;
+}
+// the look-ahead window type that goes with a stream type
+template <class RngT> struct rng_window { typedef UniformWindow type; };
+template <> struct rng_window<CounterStream> { typedef NoWindow type; };
 
 }  // namespace lmc

@@ -317,16 +317,20 @@ __device__ inline double team_uniform(TeamT& tm, RngState& r, UniformWindow& w) 
         return window_next(r, w);
     }
 }
+// LMC_RNG_COUNTER: the stream is a pure function and lives in registers; every wave of a team computes the same values
+// redundantly -- no barrier, no twist, no broadcast
+template <class TeamT>
+__device__ __forceinline__ double team_uniform(TeamT&, CounterStream& r, NoWindow&) { return counter_next(r); }
 // step_rand (base_hmc.py:46,123,154-155) for  lambda s: s * np.random.uniform(lo, hi): ONE double of the chain's own
 // stream, drawn where the reference calls it -- after the momentum draw and the start state, before the trajectory
 // (np.random.uniform(lo, hi) = lo + (hi - lo) * random_sample())
 // step_jitter == 2: an arbitrary Python step_rand callable, evaluated by the HOST for every chain before the (one-iteration)
 // launch; the kernel takes the value it left in A.step_override (lmc_engine_set_step_sizes).
-template <class TeamT, class CA, class PT>
-__device__ __forceinline__ double jitter_step_size(TeamT& tm, RngState& rng, const CA& A, const PT& P, int c, double step_size) {
+template <class TeamT, class RngT, class CA, class PT>
+__device__ __forceinline__ double jitter_step_size(TeamT& tm, RngT& rng, const CA& A, const PT& P, int c, double step_size) {
     if (!P.step_jitter) return step_size;
     if (P.step_jitter == 2) return first_f64(A.step_override[c]);
-    UniformWindow jw;
+    typename rng_window<RngT>::type jw;
     window_reset(jw);
     const double u = team_uniform(tm, rng, jw);
     return first_f64(step_size * (P.jitter_lo + (P.jitter_hi - P.jitter_lo) * u));
@@ -638,13 +642,13 @@ __device__ inline void hmc_transition_any(P& pol, double e0, double logp0, doubl
 }
 
 // the fused diagonal-mass kernels: the state lives in registers, the velocity is recomputed inside leapfrog<>
-template <int NS, class Target, class TeamT>
+template <int NS, class Target, class TeamT, class RngT = RngState>
 struct FusedHmcPolicy {
     static constexpr int kNS = NS;
     struct End { double q[NS], p[NS], g[NS]; };
-    TeamT& tm; const Target& tgt; const double (&var)[NS]; RngState& rng;
+    TeamT& tm; const Target& tgt; const double (&var)[NS]; RngT& rng;
     double (&q)[NS]; const double (&p0)[NS]; const double (&g0)[NS];
-    UniformWindow win;
+    typename rng_window<RngT>::type win;
     __device__ __forceinline__ double uniform() { return team_uniform(tm, rng, win); }
     __device__ __forceinline__ void start_state(End& c) const { vcopy(c.q, q); vcopy(c.p, p0); vcopy(c.g, g0); }
     __device__ __forceinline__ void leapfrog(double eps, End& c, double& energy, double& logp) {
@@ -652,12 +656,12 @@ struct FusedHmcPolicy {
     }
     __device__ __forceinline__ void accept_state(const End& c) { vcopy(q, c.q); }
 };
-template <int NS, class Target, class TeamT>
-__device__ inline void hmc_transition(TeamT& tm, const Target& tgt, const double (&var)[NS], RngState& rng,
+template <int NS, class Target, class TeamT, class RngT>
+__device__ inline void hmc_transition(TeamT& tm, const Target& tgt, const double (&var)[NS], RngT& rng,
                                       double (&q)[NS], const double (&p0)[NS], const double (&g0)[NS],
                                       double e0, double logp0, double step_size, double emax,
                                       double path_length, int max_steps, TransitionOut& out) {
-    FusedHmcPolicy<NS, Target, TeamT> pol{tm, tgt, var, rng, q, p0, g0, UniformWindow{0.0, 0, 0}};
+    FusedHmcPolicy<NS, Target, TeamT, RngT> pol{tm, tgt, var, rng, q, p0, g0, {}};   // (an empty window)
     hmc_transition_any(pol, e0, logp0, step_size, emax, path_length, max_steps, out);
 }
 
@@ -1036,8 +1040,8 @@ __device__ __forceinline__ double cascade_dots(PairCtx& cx, const double (&var)[
 // inside the group -- one set of leaf scalars (energies, divergence ballot, weights) on lanes 15 / 31 / 47 / 63 for four
 // leaves, the eighteen sums of the group in three gathers issued back to back, and nothing parked at level 1. Every sum keeps
 // its per-lane FMA order and its summation tree and every uniform its place in the stream: the forms are bit-identical.
-template <int NS, int PL, int G, class Target, class TeamT>
-__device__ inline void nuts_transition2(TeamT& tm, const Target& tgt, const double (&var)[NS], RngState& rng,
+template <int NS, int PL, int G, class Target, class TeamT, class RngT>
+__device__ inline void nuts_transition2(TeamT& tm, const Target& tgt, const double (&var)[NS], RngT& rng,
                                         PairCtx& cx, double* qrow, const double (&q)[NS],
                                         const double (&p0)[NS], const double (&g0)[NS], double e0, double logp0,
                                         double step_size, double emax, int max_depth, bool momentum_f32,
@@ -1065,7 +1069,7 @@ __device__ inline void nuts_transition2(TeamT& tm, const Target& tgt, const doub
     int depth = 0, n_leap = 0;
     bool diverging = false, turning = false, exhausted = true;
     const bool odd_lane = (lane_id() & 1) != 0;
-    UniformWindow win;
+    typename rng_window<RngT>::type win;
     window_reset(win);
 
     // Scalars of the n (1 or 2) leaves whose kinetic energy / log-density sums sit in lanes 7 / 15 (first leaf) and
@@ -1566,6 +1570,17 @@ constexpr int lds_tail_doubles(int w) {   // W >= 4: a second MT19937 buffer beh
 // when they report at most kPlanDown (hysteresis; the measured break-even is ~20: the plan costs ~2 800 cycles per iteration --
 // the momentum draw reads MT19937 through L2 -- and saves ~150 per leapfrog of a deep tree).
 constexpr int kPlanUp = 24, kPlanDown = 14;
+// LMC_RNG_COUNTER keeps no generator anywhere, so the two plans of a one-wave kernel differ only in what the 2 560 B the
+// generator used to take hold: plan 1's choice (one cold slot in LDS and stack level 2 behind it) or plan 0's (three cold
+// slots, the bytes stay free). ONE layout is built; DESIGN.md section 4 has the A/B that chose it. Teams have plan 0 only.
+#ifndef LMC_COUNTER_LDS_PLAN
+#define LMC_COUNTER_LDS_PLAN 1
+#endif
+constexpr int counter_lds_plan(int w) { return w == 1 ? LMC_COUNTER_LDS_PLAN : 0; }
+// the tail behind the subtree stack without a generator: the team exchange area and the stop word's broadcast slots
+constexpr int lds_tail_doubles_counter(int w) { return w == 1 ? 0 : 2 * w * kTeamSlots + 4; }
+template <bool C, class A, class B> struct select_type { typedef A type; };
+template <class A, class B> struct select_type<false, A, B> { typedef B type; };
 
 // ---- pieces of the iteration body shared by the diagonal and the dense-mass kernels ---------------------------
 // lmc_engine_request_stop(): the host's Ctrl-C (sampling.py:324-328, :470-471 in the reference: keep what has been drawn).
@@ -1798,7 +1813,10 @@ __device__ __forceinline__ void diag_mass_update(const CA& A, const PT& P, long 
 }
 
 // RNG = 0: the reference's stream (numpy legacy MT19937 + polar method, same-seed parity); 1: momentum from Philox
-// (philox_normals: the throughput mode, its own kernel instantiation so that the parity kernels are untouched by it)
+// (philox_normals: the throughput mode, its own kernel instantiation so that the parity kernels are untouched by it);
+// 2: LMC_RNG_COUNTER -- the momentum as under 1 and every uniform from the counter-based decision stream (lmc_rng.hpp:
+// CounterStream). That kernel neither reads nor writes the chain's MT19937 arrays, reserves no LDS for a generator and runs
+// under ONE LDS layout (counter_lds_plan), whatever PL says.
 // PL: the LDS plan (PairLds<NS, W, PL, G>). 0 keeps the MT19937 state and three cold slots in LDS -- best for shallow trees, where the
 // momentum draw is a fifth of an iteration; 1 (one-wave kernels) uses the generator in place and keeps stack level 2 in LDS
 // instead -- best for deep trees, where every other pair cascades through it. The plans differ in WHERE a chain's private data
@@ -1810,6 +1828,8 @@ __device__ __forceinline__ void diag_mass_update(const CA& A, const PT& P, long 
 // (A/B runs, the bit-identity test).
 template <int NS, int W, template <int> class TargetT, int RNG = 0, int PL = 0, int G = run_leaf_group(NS, W)>
 __global__ __launch_bounds__(64 * W, run_waves_per_simd(NS, W)) void run_kernel(ChainArrays, SamplerParams, const double* tparams) {
+    static_assert(RNG >= 0 && RNG <= 2 && (RNG != 2 || PL == 0), "the counter mode has one layout: instantiate it with PL = 0");
+    constexpr int LP = RNG == 2 ? counter_lds_plan(W) : PL;   // the PairLds plan this kernel is laid out by
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const long long t_resident = wall_clock64();   // constant-rate clock: the chain's residence time (kCtWaveTicks)
     // the two argument structs are read from the kernarg segment region by region (KernArgs above), never held by value
@@ -1821,7 +1841,7 @@ __global__ __launch_bounds__(64 * W, run_waves_per_simd(NS, W)) void run_kernel(
     const long long row = static_cast<long long>(c) * dpad;
     const int lds_doubles = P0.lds_doubles;
     Team<W> tm;
-    tm.xbuf = lds + lds_doubles + kLdsMtDoubles;
+    tm.xbuf = lds + lds_doubles + (RNG == 2 ? 0 : kLdsMtDoubles);
     tm.parity = 0;
     double* rng_bcast = tm.xbuf + 2 * W * kTeamSlots;
     const int tid = tm.tid();
@@ -1846,22 +1866,27 @@ __global__ __launch_bounds__(64 * W, run_waves_per_simd(NS, W)) void run_kernel(
     }
     // The MT19937 state lives in LDS for the whole launch (2.5 KB per wave, behind the subtree stack): the
     // momentum draw, the uniform window and the twist then cost LDS latency instead of HBM/L2 round trips.
-    RngState rng;
+    typename select_type<RNG == 2, CounterStream, RngState>::type rng;
     uint32_t* mt_glb = A0.mt + static_cast<long long>(c) * kMtN;
     uint32_t* mt_lds = reinterpret_cast<uint32_t*>(lds + lds_doubles);
     uint32_t* mt_lds2 = reinterpret_cast<uint32_t*>(rng_bcast + 4);   // W >= 4 only: the generation being twisted out of place
-    constexpr bool kMtInLds = run_mt_in_lds(W) && PL == 0;
-    if constexpr (kMtInLds) {
-        for (int i = tid; i < kMtN; i += 64 * W) mt_lds[i] = mt_glb[i];
-        tm.sync();
-        rng.mt = mt_lds;
+    constexpr bool kMtInLds = run_mt_in_lds(W) && PL == 0 && RNG != 2;
+    if constexpr (RNG == 2) {   // the stream is (seed, iteration, index): nothing of the chain's generator is touched
+        counter_begin(rng, P0.iter_begin);
     } else {
-        rng.mt = mt_glb;   // used in place (L2): the LDS it would take holds subtree-stack data instead
+        if constexpr (kMtInLds) {
+            for (int i = tid; i < kMtN; i += 64 * W) mt_lds[i] = mt_glb[i];
+            tm.sync();
+            rng.mt = mt_lds;
+        } else {
+            rng.mt = mt_glb;   // used in place (L2): the LDS it would take holds subtree-stack data instead
+        }
+        rng.pos = first_i32(A0.rng_pos[c]);
+        rng.has_gauss = first_i32(A0.rng_has_gauss[c]);
+        rng.gauss = first_f64(A0.rng_gauss[c]);
     }
-    rng.pos = first_i32(A0.rng_pos[c]);
-    rng.has_gauss = first_i32(A0.rng_has_gauss[c]);
-    rng.gauss = first_f64(A0.rng_gauss[c]);
-    const uint32_t chain_seed = RNG == 1 ? first_u32(A0.seed[c]) : 0u;
+    const uint32_t chain_seed = RNG >= 1 ? first_u32(A0.seed[c]) : 0u;
+    if constexpr (RNG == 2) rng.seed = chain_seed;
     DualAverage da;
     dual_average_load(A0, c, da);
     int iter_count = first_i32(A0.iter_count[c]);
@@ -1881,11 +1906,11 @@ __global__ __launch_bounds__(64 * W, run_waves_per_simd(NS, W)) void run_kernel(
     cx.glb = A0.scratch + static_cast<long long>(c) * A0.scratch_stride;
     cx.nlds = P0.nlds;
     cx.wave = tm.wave();
-    cx.wave_red = W > 1 ? cx.wave * PairLds<NS, W, PL, G>::kRedWave : 0;
+    cx.wave_red = W > 1 ? cx.wave * PairLds<NS, W, LP, G>::kRedWave : 0;
     cx.wave_scal = W > 1 ? cx.wave * kLevelScalDoubles : 0;
-    cx.red_lane = static_cast<int>(reinterpret_cast<size_t>((lds_double*)lds + (red_lane_init(PairLds<NS, W, PL, G>::kRedRows) + cx.wave_red)));
+    cx.red_lane = static_cast<int>(reinterpret_cast<size_t>((lds_double*)lds + (red_lane_init(PairLds<NS, W, LP, G>::kRedRows) + cx.wave_red)));
     cx.xpar = 0;
-    if (tid < kExpTableDoubles) lds[PairLds<NS, W, PL, G>::kExp + tid] = kExp2Table[2 * tid];
+    if (tid < kExpTableDoubles) lds[PairLds<NS, W, LP, G>::kExp + tid] = kExp2Table[2 * tid];
     tm.sync();
 
 #ifdef LMC_PHASE_TIMING   // diagnostic build (tools/phase_timing.py): s_memtime ticks per phase replace three counters
@@ -1907,7 +1932,8 @@ __global__ __launch_bounds__(64 * W, run_waves_per_simd(NS, W)) void run_kernel(
 
         // ---- momentum draw (quadpotential.py:221-224 / :374-376)
         double p0[NS];
-        if constexpr (RNG == 1) {
+        if constexpr (RNG == 2) counter_begin(rng, git);   // the iteration's uniforms count from k = 0
+        if constexpr (RNG >= 1) {
             double z[NS];
             philox_normals<NS>(chain_seed, git, tid, d, z);
 #pragma unroll
@@ -1956,7 +1982,7 @@ __global__ __launch_bounds__(64 * W, run_waves_per_simd(NS, W)) void run_kernel(
         TransitionOut out;
         if (P.kind == 0) {
             const int md = (tune && iter_count < 200) ? P.early_max_treedepth : P.max_treedepth;
-            nuts_transition2<NS, PL, G>(tm, tgt, vard, rng, cx, qrow, q, p0, g0, e0, logp0, step_size, P.emax, md,
+            nuts_transition2<NS, LP, G>(tm, tgt, vard, rng, cx, qrow, q, p0, g0, e0, logp0, step_size, P.emax, md,
                                  momentum_f32, out);
             vload<NS>(qrow, q);   // the proposal was written to the chain's row of A.q
             // (handing it over in registers when the last doubling accepted it measured -4 % on depth-3 trees)
@@ -2036,9 +2062,11 @@ __global__ __launch_bounds__(64 * W, run_waves_per_simd(NS, W)) void run_kernel(
         A.inv_std[row + tid * NS + s] = inv_std[s];
     }
     if (tid == 0) {
-        A.rng_pos[c] = rng.pos;
-        A.rng_has_gauss[c] = rng.has_gauss;
-        A.rng_gauss[c] = rng.gauss;
+        if constexpr (RNG != 2) {
+            A.rng_pos[c] = rng.pos;
+            A.rng_has_gauss[c] = rng.has_gauss;
+            A.rng_gauss[c] = rng.gauss;
+        }
         A.da[c * 4 + 0] = da.log_step;
         A.da[c * 4 + 1] = da.log_bar;
         A.da[c * 4 + 2] = da.hbar;

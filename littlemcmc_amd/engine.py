@@ -255,7 +255,8 @@ class Engine:
             setattr(cfg.tuning, field, int(value))
         if cfg.tuning.sub_blocks == 0 and hw_queue_cap() is not None:   # left open: at most one sub-block per hardware queue
             cfg.tuning.sub_blocks = -hw_queue_cap()
-        cfg.rng_mode = {"numpy": _abi.RNG_NUMPY, "philox": _abi.RNG_PHILOX}[rng]   # include/lmc_hip.h: LMC_RNG_*
+        cfg.rng_mode = {"numpy": _abi.RNG_NUMPY, "philox": _abi.RNG_PHILOX, "counter": _abi.RNG_COUNTER}[rng]   # include/lmc_hip.h: LMC_RNG_*
+        self.rng = rng
         # QuadPotentialDiagAdapt(dtype=...) (quadpotential.py:159,175-184); float64 runs in the general kernels
         # QuadPotentialFullAdapt(dtype=...) (quadpotential.py:484,497-509) likewise: float64 covariance, factor and momentum
         self.mass_f64 = np.dtype(mass_dtype) == np.float64 and potential in ("diag_adapt", "diag", "full_adapt")
@@ -763,6 +764,16 @@ class Engine:
         self._check(self._lib.lmc_engine_rng_draw(self._h, _abi.ptr(ops), ops.size, _abi.ptr(out)))
         return out
 
+    def counter_draws(self, iteration, n_uniforms=0):
+        """(normals [chains, dim], uniforms [chains, n_uniforms]) the counter-based streams hand iteration ``iteration``:
+        the standard normals of the momentum draw before the mass scaling, and the first ``n_uniforms`` decision uniforms
+        of rng="counter" in consumption order (lmc_engine_counter_draws). Raises on an rng="numpy" engine."""
+        normals = np.empty((self.chains, self.dim))
+        uniforms = np.empty((self.chains, int(n_uniforms)))
+        self._check(self._lib.lmc_engine_counter_draws(self._h, int(iteration), _abi.ptr(normals),
+                                                       _abi.ptr(uniforms) if n_uniforms > 0 else None, int(n_uniforms)))
+        return normals, uniforms
+
     def draw_momentum(self):
         out = np.empty((self.chains, self.dim))
         self._check(self._lib.lmc_engine_draw_momentum(self._h, _abi.ptr(out)))
@@ -857,6 +868,10 @@ class EngineGroup:
 
     def set_step_jitter(self, lo, hi, enable=True):
         self._each("set_step_jitter", lo, hi, enable)
+
+    def counter_draws(self, iteration, n_uniforms=0):
+        parts = self._each("counter_draws", iteration, n_uniforms)
+        return tuple(np.concatenate([p[i] for p in parts], axis=0) for i in range(2))
 
     def set_step_sizes(self, step_sizes):
         if step_sizes is None:

@@ -6,7 +6,7 @@ csrc/lmc_sampler.hpp."""
 import numpy as np
 
 from . import _abi
-from .base_hmc import BaseHMC
+from .base_hmc import BaseHMC, check_rng
 from .report import SamplerWarning, WarningType
 
 __all__ = ["NUTS"]
@@ -36,7 +36,7 @@ class NUTS(BaseHMC):
     def __init__(self, logp_dlogp_func, model_ndim=None, scaling=None, is_cov=False, potential=None,
                  target_accept=0.8, Emax=1000, adapt_step_size=True, step_scale=0.25, gamma=0.05, k=0.75,
                  t0=10, step_rand=None, path_length=2.0, max_treedepth=10, early_max_treedepth=8, size=None, momentum_rng="numpy",
-                 lds_plan="auto"):
+                 lds_plan="auto", rng="numpy"):
         if model_ndim is None:
             model_ndim = size if size is not None else getattr(logp_dlogp_func, "d", None)
         super().__init__(logp_dlogp_func=logp_dlogp_func, model_ndim=model_ndim, scaling=scaling, is_cov=is_cov,
@@ -44,6 +44,7 @@ class NUTS(BaseHMC):
                          adapt_step_size=adapt_step_size, step_scale=step_scale, gamma=gamma, k=k, t0=t0,
                          step_rand=step_rand)
         self._lds_plan = lds_plan           # include/lmc_hip.h: LMC_LDS_PLAN_* ("auto" / "shallow" / "deep"); results do not depend on it
+        self._rng = check_rng(rng)          # "counter": every random number of a transition from the counter-based streams
         self._momentum_rng = momentum_rng   # "numpy": the reference's stream; "philox": counter-based throughput mode (include/lmc_hip.h)
         self.max_treedepth = max_treedepth
         self.early_max_treedepth = early_max_treedepth

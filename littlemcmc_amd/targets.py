@@ -150,10 +150,13 @@ class UserTarget(DeviceTarget):
         h.update(extra.encode())
         return h.hexdigest()[:16]
 
-    def kernels_for(self, unit_ns, run_ns, run_w, general=False):
+    def kernels_for(self, unit_ns, run_ns, run_w, general=False, counter=False):
         """(code object, run name, trajectory name, logp name, run name under LDS plan 1 or None) for one engine shape,
-        compiled once and cached."""
-        key = (int(unit_ns), int(run_ns), int(run_w), int(bool(general)))
+        compiled once and cached. ``counter``: the sampling kernel of an rng="counter" engine, run_kernel<NS, W, UserTarget, 2>
+        (one LDS layout: no plan-1 kernel)."""
+        key = (int(unit_ns), int(run_ns), int(run_w), int(bool(general)), int(bool(counter)))
+        if key[3] and key[4]:
+            raise ValueError("rng='counter' runs in the fused kernels only")
         if key in self._code:
             return self._code[key]
         if key[3]:   # the general kernels (csrc/lmc_wide.hpp): model_ndim > 1024, dense mass matrices, float64 masses
@@ -168,23 +171,25 @@ class UserTarget(DeviceTarget):
                   "template __global__ void wide_logp_kernel<%d, %d, UserTarget>(ChainArrays, const double*, const double*, double*, double*);\n"
                   "}\n" % (key[1], key[2], key[0], key[2], key[0], key[2]))
         else:
-            names = ["lmc::run_kernel<%d, %d, lmc::UserTarget>" % (key[1], key[2]),
+            run_args = "%d, %d, %sUserTarget%s" % (key[1], key[2], "%s", ", 2" if key[4] else "")
+            names = ["lmc::run_kernel<%s>" % (run_args % "lmc::"),
                      "lmc::trajectory_kernel<%d, lmc::UserTarget>" % key[0],
                      "lmc::logp_kernel<%d, lmc::UserTarget>" % key[0]]
             tu = ('#include "lmc_sampler.hpp"\n#include "lmc_unit_kernels.hpp"\n' + self.source +
                   "\nnamespace lmc {\n"
-                  "template __global__ void run_kernel<%d, %d, UserTarget>(ChainArrays, SamplerParams, const double*);\n"
+                  "template __global__ void run_kernel<%s>(ChainArrays, SamplerParams, const double*);\n"
                   "template __global__ void trajectory_kernel<%d, UserTarget>(ChainArrays, const double*, const double*, const double*, "
                   "int, int, double, int, int, double*, double*, double*, double*, double*, double*);\n"
                   "template __global__ void logp_kernel<%d, UserTarget>(ChainArrays, const double*, const double*, double*, double*);\n"
-                  "}\n" % (key[1], key[2], key[0], key[0]))
-            if key[2] == 1:   # one-wave kernels: also the deep-tree LDS plan (csrc/lmc_sampler.hpp: run_kernel<.., PL = 1>)
+                  "}\n" % (run_args % "", key[0], key[0]))
+            if key[2] == 1 and not key[4]:   # one-wave kernels: also the deep-tree LDS plan (csrc/lmc_sampler.hpp: run_kernel<.., PL = 1>)
                 names.append("lmc::run_kernel<%d, 1, lmc::UserTarget, 0, 1>" % key[1])
                 tu += ("namespace lmc {\ntemplate __global__ void run_kernel<%d, 1, UserTarget, 0, 1>(ChainArrays, SamplerParams, "
                        "const double*);\n}\n" % key[1])
         cache = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_user_targets")
         os.makedirs(cache, exist_ok=True)
-        path = os.path.join(cache, "user_%s_%d_%d_%d%s.hsaco" % (self._digest("hiprtc"), key[0], key[1], key[2], "g" if key[3] else ""))
+        path = os.path.join(cache, "user_%s_%d_%d_%d%s.hsaco" % (self._digest("hiprtc"), key[0], key[1], key[2],
+                                                                 "g" if key[3] else "c" if key[4] else ""))
         lowered = None
         if os.path.exists(path) and os.path.exists(path + ".names"):
             with open(path, "rb") as fh:
@@ -212,7 +217,8 @@ class UserTarget(DeviceTarget):
         ns, rns, rw = C.c_int32(), C.c_int32(), C.c_int32()
         engine._check(engine._lib.lmc_engine_kernel_shape(engine._h, C.byref(ns), C.byref(rns), C.byref(rw)))
         general = bool(engine._lib.lmc_engine_uses_general_kernels(engine._h))
-        code, run, traj, logp, run1 = self.kernels_for(ns.value, rns.value, rw.value, general)
+        counter = int(engine.cfg.rng_mode) == _abi.RNG_COUNTER
+        code, run, traj, logp, run1 = self.kernels_for(ns.value, rns.value, rw.value, general, counter)
         buf = C.create_string_buffer(code, len(code))
         engine._check(engine._lib.lmc_engine_load_user_kernels(engine._h, buf, run.encode(), traj.encode(), logp.encode()))
         if run1 is not None:   # the sampling kernel under the deep-tree LDS plan: the engine may now choose per launch
