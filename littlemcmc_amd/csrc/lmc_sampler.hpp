@@ -884,17 +884,62 @@ __device__ __forceinline__ double exp_lanes(const PairCtx& cx, const ExpLanesCon
 }
 
 // ---- cold slots and subtree-stack levels: LDS offsets are immediates, the scratch row takes what does not fit
+// A vector of the scratch row is addressed as  wave-uniform base (an SGPR pair) + this lane's 32-bit byte offset + an
+// immediate: the scalar-base form of global_load/store_dwordx4, no per-lane 64-bit address is formed on the VALU. `base` is
+// the chain's row plus whatever is uniform (cold slot 0, or a stack level); OFF (doubles) selects the vector. An OFF whose
+// last byte lies beyond the instruction's signed 13-bit offset field (four-element slices, teams) is added on the scalar
+// unit instead. row_ref makes both parts opaque where a node's arm begins:
+//   * the base, so that it is an SGPR pair one scalar add away from the row pointer -- left to itself the optimiser would
+//     rather keep a finished per-lane address per vector alive (and spilled) across the pair loop;
+//   * the lane offset, so that its zero extension stands in the block of the access. Instruction selection works block by
+//     block: the extension of a shared lane offset is hoisted to another block, and every access then is a 64-bit VALU add
+//     of the base after all. The price is one v_mov_b32 per arm (not per vector).
+typedef __attribute__((address_space(1))) char glb_char;
+struct RowRef {
+    const glb_double* base;   // wave-uniform
+    unsigned lane;            // this lane's byte offset
+};
+template <int NS>
+__device__ __forceinline__ RowRef row_ref(const glb_double* base) {
+    RowRef r;
+    r.base = base;
+    r.lane = static_cast<unsigned>(LMC_CHAIN_THREAD) * (NS * 8u);
+    asm volatile("" : "+s"(r.base), "+v"(r.lane));
+    return r;
+}
+template <int NS, int OFF>
+__device__ __forceinline__ glb_double* row_vec(const RowRef& r) {
+    constexpr bool kImm = OFF * 8 >= -4096 && (OFF + NS) * 8 <= 4096;
+    const glb_double* b = r.base;
+    if constexpr (!kImm) {
+        b = r.base + OFF;
+        asm volatile("" : "+s"(b));
+    }
+    return (glb_double*)((glb_char*)b + r.lane) + (kImm ? OFF : 0);
+}
+template <int NS, int OFF>
+__device__ __forceinline__ void row_load(const RowRef& r, double (&x)[NS]) {
+    const glb_double* p = row_vec<NS, OFF>(r);
+#pragma unroll
+    for (int s = 0; s < NS; ++s) x[s] = p[s];
+}
+template <int NS, int OFF>
+__device__ __forceinline__ void row_store(const RowRef& r, const double (&x)[NS]) {
+    glb_double* p = row_vec<NS, OFF>(r);
+#pragma unroll
+    for (int s = 0; s < NS; ++s) p[s] = x[s];
+}
 template <int NS, int W, int PL, int G, int SLOT>
 __device__ __forceinline__ void cold_load(const PairCtx& cx, double (&x)[NS]) {
     using L = PairLds<NS, W, PL, G>;
     if constexpr (SLOT < L::kColdLds) vload_as<NS>((lds_double*)cx.lds + (L::kCold + SLOT * L::DP), x);
-    else vload_as<NS>((glb_double*)cx.glb + (SLOT - L::kColdLds) * L::DP, x);
+    else row_load<NS, (SLOT - L::kColdLds) * L::DP>(row_ref<NS>((const glb_double*)cx.glb), x);
 }
 template <int NS, int W, int PL, int G, int SLOT>
 __device__ __forceinline__ void cold_store(const PairCtx& cx, const double (&x)[NS]) {
     using L = PairLds<NS, W, PL, G>;
     if constexpr (SLOT < L::kColdLds) vstore_as<NS>((lds_double*)cx.lds + (L::kCold + SLOT * L::DP), x);
-    else vstore_as<NS>((glb_double*)cx.glb + (SLOT - L::kColdLds) * L::DP, x);
+    else row_store<NS, (SLOT - L::kColdLds) * L::DP>(row_ref<NS>((const glb_double*)cx.glb), x);
 }
 // level 1 (always LDS): {lp, rp, q}
 template <int NS, int W = 1, int PL = 0, int G = 2>
@@ -911,42 +956,78 @@ __device__ __forceinline__ void level1_store(const PairCtx& cx, const double (&l
     lds_double* b = (lds_double*)cx.lds + L::kL1;
     vstore_as<NS>(b, lp); vstore_as<NS>(b + L::DP, rp); vstore_as<NS>(b + 2 * L::DP, pq);
 }
-// offset (doubles) of vector v of level j > nlds in the scratch row. Opaque to the optimiser on purpose: a
-// loop-invariant level (the peeled j = 2) would otherwise get its per-lane 64-bit address precomputed outside the pair
-// loop and kept in (spilled) registers; this way the access is scalar base + uniform offset + the lane-offset register
-template <int NS, int W = 1, int PL = 0, int G = 2>
-__device__ __forceinline__ unsigned glb_level_offset(const PairCtx& cx, int j, int v) {
-    using L = PairLds<NS, W, PL, G>;
-    unsigned off = L::kGlbLevels + static_cast<unsigned>(j - cx.nlds - 1) * (4u * L::DP) + static_cast<unsigned>(v) * L::DP;
-    asm volatile("" : "+s"(off));
-    return off;
-}
-// levels j >= 2: {lp, rp, psum, q}; vector index v in 0..3
-template <int NS, int W = 1, int PL = 0, int G = 2>
-__device__ __forceinline__ void levelN_load(const PairCtx& cx, int j, int v, double (&x)[NS]) {
-    using L = PairLds<NS, W, PL, G>;
-    int nl = cx.nlds;
-    asm volatile("" : "+s"(nl));   // compared afresh (one s_cmp): hoisted, the loop-invariant test lives in a spilled lane mask
-    if (j <= nl) vload_as<NS>((lds_double*)cx.lds + (L::kL2 + (j - 2) * 4 * L::DP + v * L::DP), x);
-    else vload_as<NS>((glb_double*)cx.glb + glb_level_offset<NS, W, PL, G>(cx, j, v), x);
-}
-template <int NS, int W = 1, int PL = 0, int G = 2>
-__device__ __forceinline__ void levelN_store(const PairCtx& cx, int j, int v, const double (&x)[NS]) {
-    using L = PairLds<NS, W, PL, G>;
+// Levels j >= 2: {lp, rp, psum, q}, vectors 0..3 of a node. Where a level lives is decided ONCE per node -- one scalar
+// compare and one branch -- and each arm is straight-line code with the vector index as an immediate offset.
+// The comparison is made afresh where it is used (one s_cmp): hoisted, the loop-invariant test lives in a spilled lane mask.
+__device__ __forceinline__ bool level_in_lds(const PairCtx& cx, int j) {
     int nl = cx.nlds;
     asm volatile("" : "+s"(nl));
-    if (j <= nl) vstore_as<NS>((lds_double*)cx.lds + (L::kL2 + (j - 2) * 4 * L::DP + v * L::DP), x);
-    else vstore_as<NS>((glb_double*)cx.glb + glb_level_offset<NS, W, PL, G>(cx, j, v), x);
+    return j <= nl;
 }
-// left-end momentum / proposal position of any level j >= 1
+// offset (doubles) in LDS of vector 0 (the left-end momentum) of level j, 1 <= j <= nlds
 template <int NS, int W = 1, int PL = 0, int G = 2>
-__device__ __forceinline__ void level_load_lp(const PairCtx& cx, int j, double (&x)[NS]) {
-    if (j == 1) vload_as<NS>((lds_double*)cx.lds + PairLds<NS, W, PL, G>::kL1, x); else levelN_load<NS, W, PL, G>(cx, j, 0, x);
+__device__ __forceinline__ int level_lds_offset(int j) {
+    using L = PairLds<NS, W, PL, G>;
+    return j == 1 ? L::kL1 : L::kL2 + (j - 2) * 4 * L::DP;
+}
+// wave-uniform pointer to level j > nlds in the scratch row. Opaque to the optimiser on purpose: a loop-invariant level
+// (the peeled j = 2) would otherwise get its per-lane 64-bit addresses precomputed outside the pair loop and kept in
+// (spilled) registers; this way a level costs one scalar 64-bit add and every access is that SGPR pair + the lane-offset
+// register + an immediate (row_vec)
+template <int NS, int W = 1, int PL = 0, int G = 2>
+__device__ __forceinline__ RowRef level_row(const PairCtx& cx, int j) {
+    using L = PairLds<NS, W, PL, G>;
+    return row_ref<NS>((const glb_double*)cx.glb + (L::kGlbLevels + static_cast<unsigned>(j - cx.nlds - 1) * (4u * L::DP)));
+}
+// cascade read: node j >= 2 = {lp, rp, psum} and, if want_tl, the left-end momentum of level j - 1 >= 1 (the in-flight
+// node's left end), which sits one node below: in the row as well, or -- j = nlds + 1 -- in LDS
+template <int NS, int W = 1, int PL = 0, int G = 2>
+__device__ __forceinline__ void level_node_load(const PairCtx& cx, int j, bool want_tl, double (&lp)[NS], double (&rp)[NS],
+                                                double (&ps)[NS], double (&tl)[NS]) {
+    using L = PairLds<NS, W, PL, G>;
+    if (level_in_lds(cx, j)) {
+        lds_double* b = (lds_double*)cx.lds + level_lds_offset<NS, W, PL, G>(j);
+        vload_as<NS>(b, lp); vload_as<NS>(b + L::DP, rp); vload_as<NS>(b + 2 * L::DP, ps);
+        if (want_tl) vload_as<NS>((lds_double*)cx.lds + level_lds_offset<NS, W, PL, G>(j - 1), tl);
+    } else {
+        const RowRef b = level_row<NS, W, PL, G>(cx, j);
+        row_load<NS, 0>(b, lp); row_load<NS, L::DP>(b, rp); row_load<NS, 2 * L::DP>(b, ps);
+        if (want_tl) {
+            if (level_in_lds(cx, j - 1)) vload_as<NS>((lds_double*)cx.lds + level_lds_offset<NS, W, PL, G>(j - 1), tl);
+            else row_load<NS, -4 * L::DP>(b, tl);
+        }
+    }
+}
+// park write: node j >= 2 = {lp, rp, psum, q}. All four vectors must be in registers: the stores of an arm issue back to back
+template <int NS, int W = 1, int PL = 0, int G = 2>
+__device__ __forceinline__ void level_node_store(const PairCtx& cx, int j, const double (&lp)[NS], const double (&rp)[NS],
+                                                 const double (&ps)[NS], const double (&pq)[NS]) {
+    using L = PairLds<NS, W, PL, G>;
+    if (level_in_lds(cx, j)) {
+        lds_double* b = (lds_double*)cx.lds + level_lds_offset<NS, W, PL, G>(j);
+        vstore_as<NS>(b, lp); vstore_as<NS>(b + L::DP, rp); vstore_as<NS>(b + 2 * L::DP, ps); vstore_as<NS>(b + 3 * L::DP, pq);
+    } else {
+        const RowRef b = level_row<NS, W, PL, G>(cx, j);
+        row_store<NS, 0>(b, lp); row_store<NS, L::DP>(b, rp); row_store<NS, 2 * L::DP>(b, ps); row_store<NS, 3 * L::DP>(b, pq);
+    }
+}
+// the two vectors a park loads are in registers from here on: whatever wait they need stands in front of the first store
+template <int NS>
+__device__ __forceinline__ void park_operands_ready(double (&tl)[NS], double (&tqv)[NS]) {
+#pragma unroll
+    for (int s = 0; s < NS; ++s) asm volatile("" : "+v"(tl[s]), "+v"(tqv[s]));
+}
+// one vector of a level: V = 0 the left-end momentum of any level j >= 1, V = 3 (2 at level 1) the proposal position
+template <int NS, int W, int PL, int G, int V>
+__device__ __forceinline__ void level_vec_load(const PairCtx& cx, int j, double (&x)[NS]) {
+    using L = PairLds<NS, W, PL, G>;
+    if (level_in_lds(cx, j)) vload_as<NS>((lds_double*)cx.lds + (level_lds_offset<NS, W, PL, G>(j) + (j == 1 && V == 3 ? 2 : V) * L::DP), x);
+    else row_load<NS, V * L::DP>(level_row<NS, W, PL, G>(cx, j), x);
 }
 template <int NS, int W = 1, int PL = 0, int G = 2>
-__device__ __forceinline__ void level_load_q(const PairCtx& cx, int j, double (&x)[NS]) {
-    if (j == 1) vload_as<NS>((lds_double*)cx.lds + (PairLds<NS, W, PL, G>::kL1 + 2 * PairLds<NS, W, PL, G>::DP), x); else levelN_load<NS, W, PL, G>(cx, j, 3, x);
-}
+__device__ __forceinline__ void level_load_lp(const PairCtx& cx, int j, double (&x)[NS]) { level_vec_load<NS, W, PL, G, 0>(cx, j, x); }
+template <int NS, int W = 1, int PL = 0, int G = 2>
+__device__ __forceinline__ void level_load_q(const PairCtx& cx, int j, double (&x)[NS]) { level_vec_load<NS, W, PL, G, 3>(cx, j, x); }
 template <int NS, int W = 1, int PL = 0, int G = 2>
 __device__ __forceinline__ void level_scal_put(const PairCtx& cx, int j, double w, double a, double pe, double plogp) {
     if (lane_id() == 0) {
@@ -1233,8 +1314,7 @@ __device__ inline void nuts_transition2(TeamT& tm, const Target& tgt, const doub
                 // ---- cascade levels 2..m: node a = stack[j]; the in-flight node's left end is stack[j-1]'s
                 for (int j = 2; j <= m; ++j) {
                     double blp[NS], brp[NS], bps[NS], tl[NS];
-                    levelN_load<NS, W, PL, G>(cx, j, 0, blp); levelN_load<NS, W, PL, G>(cx, j, 1, brp); levelN_load<NS, W, PL, G>(cx, j, 2, bps);
-                    level_load_lp<NS, W, PL, G>(cx, j - 1, tl);
+                    level_node_load<NS, W, PL, G>(cx, j, true, blp, brp, bps, tl);
                     double bw, ba;
                     level_scal_get_wa<NS, W, PL, G>(cx, j, bw, ba);
                     const double sj = cascade_dots<NS, W, PL, G>(cx, var, blp, brp, bps, tl, tps, v);
@@ -1252,29 +1332,22 @@ __device__ inline void nuts_transition2(TeamT& tm, const Target& tgt, const doub
                     if (qsrc == -1) vcopy(tqv, cq);
                     else if (qsrc == -2) vcopy(tqv, eq);
                     else level_load_q<NS, W, PL, G>(cx, qsrc, tqv);
-#ifndef LMC_PARK_REORDER_MIN_NS
-#define LMC_PARK_REORDER_MIN_NS 4
-#endif
-                    // Four-element slices (C4, C5: trees that live in the scratch row from level 2 on, and in C5 single chains
-                    // whose 4 095-leapfrog trees are what a launch ends with): the node's scalars (LDS) go first and both loaded
-                    // vectors are in registers before the node's FIRST scratch-row store. Left to itself the compiler waits for
-                    // tqv's load right before the fourth store and again at the scalars, and at those joins of LDS / scratch-row
-                    // paths the wait is "everything outstanding" -- the acknowledgement of the stores just issued (found reading
-                    // the ISA, round 4). Measured, alternating runs on one box (profiles/r04_iteration_tail_ab.txt, box 3): C5
-                    // +1 ... +2 %, C4 equal; C3 (two-element slices) -0.1 ... -0.4 %, hence the condition.
-                    constexpr bool kParkReorder = NS >= LMC_PARK_REORDER_MIN_NS;
-                    if constexpr (kParkReorder) level_scal_park<NS, W, PL, G>(cx, m + 1, tw, ta, qsrc, elane, en_last, lp_last);
+                    // Both loaded vectors are in registers before the node's FIRST store (park_operands_ready), for every slice
+                    // width. Left to itself the compiler waits for tqv's load right before the fourth store and again at the
+                    // scalars, and where an LDS and a scratch-row path join the wait is "everything outstanding" -- the
+                    // acknowledgement of the stores just issued (found reading the ISA, round 4). With one placement decision
+                    // per node the stores of either arm are straight-line code. Where the node's scalars (LDS) go is what was
+                    // measured (profiles/r04_iteration_tail_ab.txt): in front of the stores for four-element slices (C5 +1 ...
+                    // +2 %, C4 equal), behind them for narrower ones (in front: C3 -0.1 ... -0.4 %), as in the quad form.
+                    constexpr bool kScalarsFirst = NS >= 4;
+                    if constexpr (kScalarsFirst) level_scal_park<NS, W, PL, G>(cx, m + 1, tw, ta, qsrc, elane, en_last, lp_last);
                     if (m == 0) {
                         level1_store<NS, W, PL, G>(cx, tl, cp, tqv);
                     } else {
-                        if constexpr (kParkReorder) {
-#pragma unroll
-                            for (int s = 0; s < NS; ++s) asm volatile("" : "+v"(tl[s]), "+v"(tqv[s]));
-                        }
-                        levelN_store<NS, W, PL, G>(cx, m + 1, 0, tl); levelN_store<NS, W, PL, G>(cx, m + 1, 1, cp);
-                        levelN_store<NS, W, PL, G>(cx, m + 1, 2, tps); levelN_store<NS, W, PL, G>(cx, m + 1, 3, tqv);
+                        park_operands_ready<NS>(tl, tqv);
+                        level_node_store<NS, W, PL, G>(cx, m + 1, tl, cp, tps, tqv);
                     }
-                    if constexpr (!kParkReorder) level_scal_park<NS, W, PL, G>(cx, m + 1, tw, ta, qsrc, elane, en_last, lp_last);
+                    if constexpr (!kScalarsFirst) level_scal_park<NS, W, PL, G>(cx, m + 1, tw, ta, qsrc, elane, en_last, lp_last);
                 }
                 }   // G == 2
             }
@@ -1425,8 +1498,8 @@ __device__ inline void nuts_transition2(TeamT& tm, const Target& tgt, const doub
                 const int m = 1 + __builtin_ctz(~static_cast<unsigned>(k) | (1u << (D - 2)));
                 for (int j = 2; j <= m; ++j) {
                     double blp[NS], brp[NS], bps[NS], tl[NS];
-                    levelN_load<NS, W, PL, G>(cx, j, 0, blp); levelN_load<NS, W, PL, G>(cx, j, 1, brp); levelN_load<NS, W, PL, G>(cx, j, 2, bps);
-                    if (j == 2) vcopy(tl, a0); else levelN_load<NS, W, PL, G>(cx, j - 1, 0, tl);
+                    level_node_load<NS, W, PL, G>(cx, j, j > 2, blp, brp, bps, tl);
+                    if (j == 2) vcopy(tl, a0);
                     double bw, ba;
                     level_scal_get_wa<NS, W, PL, G>(cx, j, bw, ba);
                     const double sj = cascade_dots<NS, W, PL, G>(cx, var, blp, brp, bps, tl, tps, v);
@@ -1440,10 +1513,12 @@ __device__ inline void nuts_transition2(TeamT& tm, const Target& tgt, const doub
                 if (turning) break;
                 if (k + 1 < n_quads) {   // park the node at level m + 1 >= 2
                     double tl[NS], tqv[NS];
-                    if (m == 1) vcopy(tl, a0); else levelN_load<NS, W, PL, G>(cx, m, 0, tl);
+                    if (m == 1) vcopy(tl, a0); else level_load_lp<NS, W, PL, G>(cx, m, tl);
                     prop_q(tqv);
-                    levelN_store<NS, W, PL, G>(cx, m + 1, 0, tl); levelN_store<NS, W, PL, G>(cx, m + 1, 1, cp);
-                    levelN_store<NS, W, PL, G>(cx, m + 1, 2, tps); levelN_store<NS, W, PL, G>(cx, m + 1, 3, tqv);
+                    // both loaded vectors in registers, then the four stores and the scalars back to back (see the pair form's
+                    // park: two-element slices at most here, so the scalars stay behind the stores)
+                    park_operands_ready<NS>(tl, tqv);
+                    level_node_store<NS, W, PL, G>(cx, m + 1, tl, cp, tps, tqv);
                     level_scal_park<NS, W, PL, G>(cx, m + 1, tw, ta, qsrc, elane, en_last, lp_last);
                 } else if (D == 2) {
                     // the subtree's left end for the trajectory-level test: rows 6 / 7 of the reduction buffer, which nothing

@@ -123,6 +123,8 @@ def kind_of(op):
         return "smem"
     if op.startswith(("s_waitcnt", "s_nop")):
         return "wait"
+    if op.startswith(("s_cbranch", "s_branch")):
+        return "branch"   # (counted apart from the other SALU work: a branch also ends the wave's instruction group)
     if op.startswith("s_"):
         return "salu"
     return "other"
@@ -182,10 +184,10 @@ def main():
             return "reduce", 1.0
         if fn in ("exp_lanes", "exp_lanes_const", "exp_uniform", "exp_uniform_fast", "fma_sgpr_addend", "sgpr_const") or f == "__clang_hip_math.h":
             return ("rare", 0.0) if fn in ("exp_uniform", "exp_uniform_fast") else ("leaf scalars", 1.0)
-        if fn in ("cascade_dots", "level1_load", "levelN_load", "level_load_lp", "level_load_q", "level_scal_get_wa", "level_scal_get",
-                  "glb_level_offset", "vload_as", "cold_load"):
+        if fn in ("cascade_dots", "level1_load", "level_node_load", "level_vec_load", "level_load_lp", "level_load_q", "level_scal_get_wa",
+                  "level_scal_get", "level_in_lds", "level_lds_offset", "level_row", "row_ref", "row_vec", "row_load", "vload_as", "cold_load"):
             return "merge: cascade levels (dots, parked-node loads)", 1.0
-        if fn in ("level1_store", "levelN_store", "level_scal_park", "level_scal_put", "vstore_as", "cold_store"):
+        if fn in ("level1_store", "level_node_store", "park_operands_ready", "row_store", "level_scal_park", "level_scal_put", "vstore_as", "cold_store"):
             return "park", 0.5
         if f == "lmc_sampler.hpp" and fn == "nuts_transition2":
             if L_rare0 <= ln < L_rare1:
@@ -245,14 +247,14 @@ def main():
             tot[("%s [%s]" % (name, rname), w)][kind_of(op)] += 1
     print("kernel %s" % kernel)
     print("pair loop: %d basic blocks of %d, %d instructions (static)" % (len(loop), len(order), sum(sum(c.values()) for c in tot.values())))
-    print("%-86s %6s %6s %6s %5s %5s %5s %5s | %s" % ("bucket", "weight", "valu", "salu", "lds", "vmem", "smem", "wait", "weighted, per LEAPFROG (a pair = 2)"))
+    print("%-86s %6s %6s %6s %6s %5s %5s %5s %5s | %s" % ("bucket", "weight", "valu", "salu", "branch", "lds", "vmem", "smem", "wait", "weighted, per LEAPFROG (a pair = 2)"))
     grand = 0.0
     for (name, w), c in sorted(tot.items(), key=lambda kv: -sum(kv[1].values()) * kv[0][1]):
         n = sum(c.values())
         per = 0.5 * w * n
         grand += per
-        print("%-86s %6.3f %6d %6d %5d %5d %5d %5d | %6.1f" % (name, w, c["valu"], c["salu"], c["lds"], c["vmem"], c["smem"], c["wait"], per))
-    print("%-86s %6s %6s %6s %5s %5s %5s %5s | %6.1f" % ("TOTAL (weighted)", "", "", "", "", "", "", "", grand))
+        print("%-86s %6.3f %6d %6d %6d %5d %5d %5d %5d | %6.1f" % (name, w, c["valu"], c["salu"], c["branch"], c["lds"], c["vmem"], c["smem"], c["wait"], per))
+    print("%-86s %6s %6s %6s %6s %5s %5s %5s %5s | %6.1f" % ("TOTAL (weighted)", "", "", "", "", "", "", "", "", grand))
 
 
 def main_quads(asm, kernel, line_of):
@@ -328,13 +330,13 @@ def main_quads(asm, kernel, line_of):
                 scratch.append((b, loc, t))
     print("kernel %s" % kernel)
     print("quad loop: %d basic blocks of %d, %d instructions (static)" % (len(loop), len(order), sum(sum(c.values()) for c in tot.values())))
-    print("%-52s %6s %6s %6s %5s %5s %5s %5s | %s" % ("region", "weight", "valu", "salu", "lds", "vmem", "smem", "wait", "weighted, per LEAPFROG (a quad = 4)"))
+    print("%-52s %6s %6s %6s %6s %5s %5s %5s %5s | %s" % ("region", "weight", "valu", "salu", "branch", "lds", "vmem", "smem", "wait", "weighted, per LEAPFROG (a quad = 4)"))
     grand = 0.0
     for (name, w), c in sorted(tot.items(), key=lambda kv: -sum(kv[1].values()) * kv[0][1]):
         per = 0.25 * w * sum(c.values())
         grand += per
-        print("%-52s %6.3f %6d %6d %5d %5d %5d %5d | %6.1f" % (name, w, c["valu"], c["salu"], c["lds"], c["vmem"], c["smem"], c["wait"], per))
-    print("%-52s %6s %6s %6s %5s %5s %5s %5s | %6.1f" % ("TOTAL (weighted)", "", "", "", "", "", "", "", grand))
+        print("%-52s %6.3f %6d %6d %6d %5d %5d %5d %5d | %6.1f" % (name, w, c["valu"], c["salu"], c["branch"], c["lds"], c["vmem"], c["smem"], c["wait"], per))
+    print("%-52s %6s %6s %6s %6s %5s %5s %5s %5s | %6.1f" % ("TOTAL (weighted)", "", "", "", "", "", "", "", "", grand))
     print("scratch instructions in the quad loop: %d" % len(scratch))
     for b, loc, t in scratch:
         print("  %s %s %s" % (b, loc, t))
