@@ -307,6 +307,26 @@ int lmc_engine_set_step_sizes(lmc_engine* e, const double* step_sizes);
  * function lmc_engine_run() applies after every tuning iteration. The dense counterpart is lmc_engine_dense_update(). */
 int lmc_engine_diag_update(lmc_engine* e, int32_t tune);
 int lmc_engine_reserve(lmc_engine* e, int64_t capacity, int64_t trace_begin);
+/* Thinning: reserve() for a job that keeps every thin-th draw. Of the iterations trace_begin, trace_begin + 1, ... the
+ * sampling kernels store trace_begin, trace_begin + thin, trace_begin + 2 thin, ...: the trace -- in HBM or attached
+ * (lmc_engine_attach_trace) -- has ceil((capacity - trace_begin) / thin) rows per chain (lmc_engine_trace_rows), row r
+ * holding iteration trace_begin + r * thin, and the discarded draws are never written anywhere. lmc_engine_reserve() is
+ * thin = 1. Nothing else changes: the per-draw statistic records stay [chains][capacity], one per ITERATION (counters,
+ * lmc_engine_get_stat_*() and the tuned-step statistics need every one of them; at 64 bytes each they are not what fills
+ * memory) -- lmc_engine_copy_window_strided_async() exports the kept ones -- and adaptation, moments and counters see every
+ * draw. thin < 1 is LMC_ERR_INVALID. On a thinned engine lmc_engine_get_trace(dst, iter_begin, n_iters) delivers the kept
+ * iterations inside [iter_begin, iter_begin + n_iters), in order (dst: [chains][that many][dim]).
+ * Limits: with thin > 1 the capacity may be at most 2^29 iterations (LMC_ERR_INVALID beyond: the kernels count kept draws
+ * in 32 bits). A thin larger than the capacity keeps iteration trace_begin alone, exactly like thin = capacity, and is
+ * applied as such inside the library; lmc_engine_thin() still returns the value as it was given. */
+int lmc_engine_reserve_thinned(lmc_engine* e, int64_t capacity, int64_t trace_begin, int64_t thin);
+int64_t lmc_engine_thin(lmc_engine* e);          /* as given to reserve_thinned(); 1 after reserve() */
+int64_t lmc_engine_trace_rows(lmc_engine* e);    /* rows per chain of the trace; 0: no trace */
+/* The arithmetic of thinning, as the library does it for every launch (pure; no engine, no device): of the iterations
+ * [first, first + n), those kept under (trace_begin, thin) are *first_kept, *first_kept + thin, ... (*n_kept of them; 0:
+ * none, *first_kept is then the next kept iteration at or after first + n), and *first_kept lies in trace row *first_row.
+ * Out pointers may be NULL. */
+int lmc_thin_window(int64_t first, int64_t n, int64_t trace_begin, int64_t thin, int64_t* first_kept, int64_t* n_kept, int64_t* first_row);
 /* Where the draws go, decided after reserve(capacity, trace_begin < 0) and possibly while the job is already running (the
  * kernel arguments of a launch are fixed when it is enqueued: launches enqueued AFTER this call store the draws of iterations
  * >= trace_begin, so call it before enqueueing the first launch that reaches trace_begin).
@@ -314,7 +334,8 @@ int lmc_engine_reserve(lmc_engine* e, int64_t capacity, int64_t trace_begin);
  *        memory: lmc_host_alloc / lmc_host_register; or device memory). The sampling kernel stores every draw THERE, one
  *        coalesced row per chain per iteration, straight over the host link as it is produced -- the array sample() returns
  *        (sampling.py:207-222) is complete when the last launch is, with no copy and no trace in HBM. The engine never frees
- *        it; lmc_engine_get_trace() / trace_device_ptr() read through it.
+ *        it; lmc_engine_get_trace() / trace_device_ptr() read through it. On a thinned engine (lmc_engine_reserve_thinned) the
+ *        array is [chains][ceil((capacity - trace_begin) / thin)][dim].
  *   dst == NULL: the engine allocates the trace in HBM (what reserve(capacity, trace_begin) does). */
 int lmc_engine_attach_trace(lmc_engine* e, double* dst, int64_t trace_begin);
 /* KeyboardInterrupt (sampling.py:324-328, :470-471: the reference keeps what has been drawn so far). stop = 1: every
@@ -390,6 +411,13 @@ typedef struct lmc_window_dst {
     lmc_window_plane plane[LMC_MAX_PLANES];
 } lmc_window_dst;
 int lmc_engine_copy_window_async(lmc_engine* e, const lmc_window_dst* dst, int64_t iter_begin, int64_t n_iters);
+/* The same for a destination that keeps every stride-th iteration: its n_out ROWS hold the iterations dst->first,
+ * dst->first + stride, ...; of the window [iter_begin, iter_begin + n_iters) the iterations with (it - dst->first) % stride
+ * == 0 are written, into row (it - dst->first) / stride of every plane (the gather kernel is indexed by destination row:
+ * it = first + row * stride). dst->trace != NULL copies the same rows out of the engine's HBM trace, which must hold exactly
+ * those iterations: stride == the engine's thin and (dst->first - trace_begin) % stride == 0, else LMC_ERR_INVALID.
+ * copy_window_async() is stride = 1. */
+int lmc_engine_copy_window_strided_async(lmc_engine* e, const lmc_window_dst* dst, int64_t iter_begin, int64_t n_iters, int64_t stride);
 int lmc_engine_copy_wait(lmc_engine* e);
 /* Page-locked host memory every visible GPU can copy into (hipHostMalloc, portable): what the arrays sample() returns live
  * in. NULL on failure (lmc_last_error(NULL)); free with lmc_host_free. */
@@ -402,7 +430,7 @@ int lmc_host_register(void* p, uint64_t bytes);
 int lmc_host_unregister(void* p);
 
 /* Device pointers of the engine-owned outputs for zero-copy consumers; valid until the next reserve()/destroy().
- * Trace: [chains][capacity - trace_begin][dim] float64. Statistics: [chains][capacity] records of LMC_STAT_RECORD_BYTES
+ * Trace: [chains][lmc_engine_trace_rows()][dim] float64 (capacity - trace_begin rows unless thinned). Statistics: [chains][capacity] records of LMC_STAT_RECORD_BYTES
  * = 64 bytes, one per draw, written by the sampling kernel in one coalesced store:
  *     bytes  0..55  the seven float64 statistics in LMC_STAT_* (f64) order
  *     bytes 56..59  int32  tree_size (NUTS) / n_steps (HMC): the leapfrog steps of the draw

@@ -137,6 +137,11 @@ _SIGNATURES = {
     "lmc_engine_reset_tuning": (C.c_int, [_P]),
     "lmc_engine_set_dual_average": (C.c_int, [_P, C.c_double, C.c_double, C.c_double, C.c_int32]),
     "lmc_engine_reserve": (C.c_int, [_P, C.c_int64, C.c_int64]),
+    "lmc_engine_reserve_thinned": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64]),
+    "lmc_engine_thin": (C.c_int64, [_P]),
+    "lmc_engine_trace_rows": (C.c_int64, [_P]),
+    "lmc_thin_window": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                  C.POINTER(C.c_int64)]),
     "lmc_engine_attach_trace": (C.c_int, [_P, _P, C.c_int64]),
     "lmc_engine_run": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int32]),
     "lmc_engine_run_streams": (C.c_int, [_P, _P, C.c_int32]),
@@ -144,6 +149,7 @@ _SIGNATURES = {
     "lmc_engine_last_run_leaf_group": (C.c_int32, [_P]),
     "lmc_engine_last_run_dense_kernel": (C.c_int32, [_P]),
     "lmc_engine_copy_window_async": (C.c_int, [_P, C.POINTER(WindowDst), C.c_int64, C.c_int64]),
+    "lmc_engine_copy_window_strided_async": (C.c_int, [_P, C.POINTER(WindowDst), C.c_int64, C.c_int64, C.c_int64]),
     "lmc_engine_copy_wait": (C.c_int, [_P]),
     "lmc_host_alloc": (_P, [C.c_uint64]),
     "lmc_host_free": (None, [_P]),

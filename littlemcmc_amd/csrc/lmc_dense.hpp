@@ -491,6 +491,7 @@ __device__ __forceinline__ void dense_run_chain(const ChainArrays& A, const Dens
     scr.dpad = dpad;
     const bool momentum_f32 = P.momentum_f32 != 0;
 
+    int kept = 0;   // draws of this launch stored so far (launch_trace_row)
     for (int it = 0; it < P.n_iters; ++it) {
         const long long git = P.iter_begin + it;
         const bool tune = git < P.n_tune;
@@ -537,7 +538,7 @@ __device__ __forceinline__ void dense_run_chain(const ChainArrays& A, const Dens
         ++iter_count;
         if (!tune) ++ct_after;
         if (A.mom_mean != nullptr && !tune) moments_update<NS>(A, tm, c, row, q);
-        write_outputs<NS>(A, c, tid, git, q, out, da.step_now, da.step_bar_now, tune);
+        write_outputs<NS>(A, c, tid, git, launch_trace_row(P, it, kept), q, out, da.step_now, da.step_bar_now, tune);
         if (first_i32(stop_word) != 0) break;
     }
 

@@ -3,6 +3,7 @@
 // instantiation, and moves results in and out. No torch, no exceptions across the boundary.
 #include <hip/hip_runtime.h>
 
+#include <climits>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -252,12 +253,15 @@ struct WindowPlanes {
     int kind[LMC_MAX_PLANES], idx[LMC_MAX_PLANES], as[LMC_MAX_PLANES];
     void* dst[LMC_MAX_PLANES];
 };
+// Strided (lmc_engine_copy_window_strided_async): the kernel is indexed by DESTINATION row -- `n` rows from row0 on, row
+// row0 + i holds iteration iter_begin + i * stride (iter_begin = the window's first kept iteration) -- so the stride costs
+// one multiply and no division.
 __global__ void window_gather_kernel(const StatRecord* rec, long long cap, int chain0, int chains, long long iter_begin, long long n, int hmc,
-                                     WindowPlanes W, long long n_out, long long row0) {
+                                     WindowPlanes W, long long n_out, long long row0, long long stride) {
     const long long total = static_cast<long long>(chains) * n;   // chains [chain0, chain0 + chains) of the engine
     for (long long k = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x; k < total; k += static_cast<long long>(gridDim.x) * blockDim.x) {
         const long long c = chain0 + k / n, i = k % n;
-        const StatRecord r = rec[c * cap + iter_begin + i];
+        const StatRecord r = rec[c * cap + iter_begin + i * stride];
         const long long o = c * n_out + row0 + i;
         for (int p = 0; p < W.n_planes; ++p) {
             void* out = W.dst[p];
@@ -353,6 +357,7 @@ struct lmc_engine {
     hipEvent_t sub_done[kMaxSub] = {};
     hipEvent_t main_done = nullptr;
     bool trace_external = false;   // A.trace is the caller's memory (lmc_engine_attach_trace): never freed here
+    long long thin = 1;            // as given to lmc_engine_reserve_thinned (A.thin is the same value capped at the capacity)
     // streamed results (lmc_engine_copy_window_async): a high-priority copy stream of the engine's own, ordered after the
     // launches enqueued so far by events (the copies are kernels that write the caller's device-accessible arrays themselves)
     hipStream_t copy_stream = nullptr;
@@ -450,6 +455,35 @@ static int fail(lmc_engine* e, int code, const char* fmt, ...) {
     g_last_error = buf;
     if (e) e->err = buf;
     return code;
+}
+
+// ---- thinning: which draws a window of iterations keeps ------------------------------------------------------------------
+// Of the iterations [first, first + n) the draws kept under (trace_begin, thin) are first_kept, first_kept + thin, ...
+// (n_kept of them), and first_kept lies in trace row first_row. The one place the library does this arithmetic: every
+// launch's kernel arguments (set_launch_window), lmc_engine_get_trace and the strided window copy come through here.
+struct ThinWindow { long long first_kept, n_kept, first_row; };
+static ThinWindow thin_window(long long first, long long n, long long trace_begin, long long thin) {
+    const long long from = first > trace_begin ? first : trace_begin;
+    const long long row = (from - trace_begin + thin - 1) / thin;          // first row at or after `from`
+    const long long it = trace_begin + row * thin;
+    ThinWindow w{it, 0, row};
+    if (it < first + n) w.n_kept = (first + n - it + thin - 1) / thin;
+    return w;
+}
+static long long trace_rows_of(long long capacity, long long trace_begin, long long thin) {
+    return (capacity - trace_begin + thin - 1) / thin;
+}
+// The launch [P.iter_begin, P.iter_begin + P.n_iters): which of its iterations store their draw, and where (lmc_sampler.hpp:
+// launch_trace_row). Called wherever a launch's iteration range is set.
+static void set_launch_window(SamplerParams& P, const ChainArrays& A) {
+    P.keep_first = INT_MAX;
+    P.thin = static_cast<int>(A.thin);
+    P.trace_row0 = 0;
+    if (!A.trace || P.n_iters <= 0) return;
+    const ThinWindow w = thin_window(P.iter_begin, P.n_iters, A.trace_begin, A.thin);
+    if (w.n_kept <= 0) return;
+    P.keep_first = static_cast<int>(w.first_kept - P.iter_begin);
+    P.trace_row0 = w.first_row;
 }
 
 #define HIP_TRY(e, call)                                                                        \
@@ -682,6 +716,7 @@ static int dense_run(lmc_engine* e, SamplerParams P) {
             SamplerParams Q = P;
             Q.iter_begin = it;
             Q.n_iters = static_cast<int>(n);
+            set_launch_window(Q, e->A);
             Q.chain_begin = static_cast<int>(lo);
             Q.relay_mask = relay_mask_for(hi - lo);
             int rc;
@@ -1026,6 +1061,7 @@ int lmc_engine_create(const lmc_config* cfg, lmc_engine** out) {
     ChainArrays& A = e->A;
     std::memset(&A, 0, sizeof(A));
     A.chains = cfg->chains;
+    A.thin = 1;
     A.d = cfg->dim;
     A.dpad = e->dpad;
     int rc = LMC_OK;
@@ -2051,8 +2087,25 @@ int lmc_engine_set_dual_average(lmc_engine* e, double log_step, double log_bar, 
     return launched(e, launch(set_da_kernel, dim3(blocks), dim3(threads), 0, main_stream(e), e->A, log_step, log_bar, hbar, count));
 }
 
+int lmc_thin_window(int64_t first, int64_t n, int64_t trace_begin, int64_t thin, int64_t* first_kept, int64_t* n_kept, int64_t* first_row) {
+    const int64_t lim = int64_t(1) << 40;   // (far beyond any job; keeps the arithmetic inside 64 bits)
+    if (first < 0 || n < 0 || trace_begin < 0 || thin < 1 || first > lim || n > lim || trace_begin > lim || thin > lim)
+        return fail(nullptr, LMC_ERR_INVALID, "thin_window: first, n, trace_begin in [0, 2^40] and thin in [1, 2^40]");
+    const ThinWindow w = thin_window(first, n, trace_begin, thin);
+    if (first_kept) *first_kept = w.first_kept;
+    if (n_kept) *n_kept = w.n_kept;
+    if (first_row) *first_row = w.first_row;
+    return LMC_OK;
+}
+
 int lmc_engine_reserve(lmc_engine* e, int64_t capacity, int64_t trace_begin) {
+    return lmc_engine_reserve_thinned(e, capacity, trace_begin, 1);
+}
+
+int lmc_engine_reserve_thinned(lmc_engine* e, int64_t capacity, int64_t trace_begin, int64_t thin) {
+    if (thin < 1) return fail(e, LMC_ERR_INVALID, "thin must be >= 1 (got %lld)", (long long)thin);   // (before anything else: no engine, no device needed)
     if (!e || capacity < 1) return fail(e, LMC_ERR_INVALID, "capacity must be >= 1");
+    if (thin > 1 && capacity > (1LL << 29)) return fail(e, LMC_ERR_INVALID, "a thinned trace takes a capacity of at most 2^29 iterations");
     const bool keep_trace = trace_begin >= 0 && trace_begin < capacity;
     HIP_TRY(e, hipSetDevice(e->cfg.device));
     HIP_TRY(e, hipStreamSynchronize(main_stream(e)));
@@ -2063,8 +2116,12 @@ int lmc_engine_reserve(lmc_engine* e, int64_t capacity, int64_t trace_begin) {
     dev_free(e, A.stat_rec); A.stat_rec = nullptr;
     const size_t C = e->cfg.chains, cap = static_cast<size_t>(capacity);
     int rc;
-    if (keep_trace && (rc = dev_alloc(e, &A.trace, C * (cap - static_cast<size_t>(trace_begin)) * e->cfg.dim, false)) != LMC_OK) return rc;
+    // (a thin beyond the capacity keeps iteration trace_begin alone, like thin = capacity: the kernels count in 32 bits)
+    e->thin = thin;
+    A.thin = thin < capacity ? thin : capacity;
     A.trace_begin = keep_trace ? trace_begin : 0;
+    A.trace_rows = keep_trace ? trace_rows_of(capacity, trace_begin, A.thin) : 0;
+    if (keep_trace && (rc = dev_alloc(e, &A.trace, C * static_cast<size_t>(A.trace_rows) * e->cfg.dim, false)) != LMC_OK) return rc;
     if ((rc = dev_alloc(e, &A.stat_rec, C * cap)) != LMC_OK) return rc;
     A.cap = capacity;
     HIP_TRY(e, hipStreamSynchronize(main_stream(e)));
@@ -2097,10 +2154,11 @@ int lmc_engine_attach_trace(lmc_engine* e, double* dst, int64_t trace_begin) {
         e->trace_external = true;
     } else {
         const size_t C = e->cfg.chains;
-        const int rc = dev_alloc(e, &A.trace, C * static_cast<size_t>(A.cap - trace_begin) * e->cfg.dim, false);
+        const int rc = dev_alloc(e, &A.trace, C * static_cast<size_t>(trace_rows_of(A.cap, trace_begin, A.thin)) * e->cfg.dim, false);
         if (rc != LMC_OK) return rc;
     }
     A.trace_begin = trace_begin;
+    A.trace_rows = trace_rows_of(A.cap, trace_begin, A.thin);
     return LMC_OK;
 }
 
@@ -2134,6 +2192,7 @@ static SamplerParams make_params(const lmc_engine* e, int64_t n_tune, int64_t it
     P.jitter_lo = e->jitter_lo;
     P.jitter_hi = e->jitter_hi;
     P.relay_mask = 255;
+    set_launch_window(P, e->A);
     return P;
 }
 
@@ -2154,6 +2213,7 @@ static int wide_run(lmc_engine* e, SamplerParams P) {
         SamplerParams Q = P;
         Q.iter_begin = it;
         Q.n_iters = static_cast<int>(adapt ? 1 : end - it);
+        set_launch_window(Q, e->A);
         int rc;
         if (rtc) {
             void* args[] = {&e->A, &e->D, &Q, &e->tparams};
@@ -2313,10 +2373,13 @@ int lmc_engine_get_trace(lmc_engine* e, double* dst, int64_t iter_begin, int64_t
     if (iter_begin < e->A.trace_begin)
         return fail(e, LMC_ERR_INVALID, "draws before iteration %lld were not stored", (long long)e->A.trace_begin);
     const size_t C = e->cfg.chains, d = e->cfg.dim;
-    const size_t rows = static_cast<size_t>(e->A.cap - e->A.trace_begin);
-    const double* src = e->A.trace + static_cast<size_t>(iter_begin - e->A.trace_begin) * d;
-    HIP_TRY(e, hipMemcpy2DAsync(dst, n_iters * d * sizeof(double), src, rows * d * sizeof(double),
-                                n_iters * d * sizeof(double), C, hipMemcpyDefault, main_stream(e)));
+    const size_t rows = static_cast<size_t>(e->A.trace_rows);
+    const ThinWindow w = thin_window(iter_begin, n_iters, e->A.trace_begin, e->A.thin);   // the kept iterations of the window, in order
+    if (w.n_kept <= 0) return LMC_OK;
+    const size_t n_rows = static_cast<size_t>(w.n_kept);
+    const double* src = e->A.trace + static_cast<size_t>(w.first_row) * d;
+    HIP_TRY(e, hipMemcpy2DAsync(dst, n_rows * d * sizeof(double), src, rows * d * sizeof(double),
+                                n_rows * d * sizeof(double), C, hipMemcpyDefault, main_stream(e)));
     HIP_TRY(e, hipStreamSynchronize(main_stream(e)));
     return LMC_OK;
 }
@@ -2382,18 +2445,32 @@ static void* device_view_of(void* p) {
 }
 
 int lmc_engine_copy_window_async(lmc_engine* e, const lmc_window_dst* dst, int64_t iter_begin, int64_t n_iters) {
+    return lmc_engine_copy_window_strided_async(e, dst, iter_begin, n_iters, 1);
+}
+
+int lmc_engine_copy_window_strided_async(lmc_engine* e, const lmc_window_dst* dst, int64_t iter_begin, int64_t n_iters, int64_t stride_given) {
+    if (stride_given < 1) return fail(e, LMC_ERR_INVALID, "stride must be >= 1 (got %lld)", (long long)stride_given);
     if (!e || !dst) return fail(e, LMC_ERR_INVALID, "null argument");
+    // (a stride beyond the capacity keeps one iteration, like the capacity itself: lmc_engine_reserve_thinned)
+    const long long stride = e->A.cap > 0 && stride_given > e->A.cap ? e->A.cap : stride_given;
     if (n_iters == 0) return LMC_OK;
     if (iter_begin < 0 || n_iters < 0 || iter_begin + n_iters > e->A.cap || !e->A.stat_rec)
         return fail(e, LMC_ERR_INVALID, "window [%lld, %lld) outside reserved capacity %lld", (long long)iter_begin,
                     (long long)(iter_begin + n_iters), (long long)e->A.cap);
-    if (iter_begin < dst->first || iter_begin + n_iters > dst->first + dst->n_out)
+    // the destination's n_out ROWS hold the iterations first, first + stride, ...: rows [first_row, first_row + n_kept) are written
+    const ThinWindow win = thin_window(iter_begin, n_iters, dst->first, stride);
+    if (iter_begin < dst->first || win.first_row + win.n_kept > dst->n_out)
         return fail(e, LMC_ERR_INVALID, "window [%lld, %lld) outside the destination's iterations [%lld, %lld)", (long long)iter_begin,
-                    (long long)(iter_begin + n_iters), (long long)dst->first, (long long)(dst->first + dst->n_out));
+                    (long long)(iter_begin + n_iters), (long long)dst->first, (long long)(dst->first + dst->n_out * stride));
     if (dst->n_planes < 0 || dst->n_planes > LMC_MAX_PLANES) return fail(e, LMC_ERR_INVALID, "n_planes %d", dst->n_planes);
     if (dst->copy_workgroups < 0 || dst->copy_workgroups > 4096) return fail(e, LMC_ERR_INVALID, "copy_workgroups %d", dst->copy_workgroups);
     if (dst->trace && (!e->A.trace || iter_begin < e->A.trace_begin))
         return fail(e, LMC_ERR_INVALID, "draws before iteration %lld were not stored", (long long)e->A.trace_begin);
+    // the HBM trace holds the engine's own kept draws: its rows are the destination's rows when both keep the same iterations
+    if (dst->trace && (stride != e->A.thin || (dst->first - e->A.trace_begin) % stride != 0))
+        return fail(e, LMC_ERR_INVALID, "trace: stride %lld from iteration %lld does not match the engine's trace (thin %lld from iteration %lld)",
+                    (long long)stride_given, (long long)dst->first, (long long)e->thin, (long long)e->A.trace_begin);
+    if (win.n_kept <= 0) return LMC_OK;
     HIP_TRY(e, hipSetDevice(e->cfg.device));
     WindowPlanes W;
     std::memset(&W, 0, sizeof(W));
@@ -2435,8 +2512,8 @@ int lmc_engine_copy_window_async(lmc_engine* e, const lmc_window_dst* dst, int64
         }
     HIP_TRY(e, hipEventRecord(e->copy_dep[lmc_engine::kMaxSub], e->stream_));
     HIP_TRY(e, hipStreamWaitEvent(cs, e->copy_dep[lmc_engine::kMaxSub], 0));
-    const long long C = e->cfg.chains, d = e->cfg.dim, n = n_iters, n_out = dst->n_out;
-    const long long row0 = iter_begin - dst->first;
+    const long long C = e->cfg.chains, d = e->cfg.dim, n = win.n_kept, n_out = dst->n_out;
+    const long long row0 = win.first_row;
     // Few workgroups of ONE wavefront each. The copy's wavefronts sit on stores that drain at host-link speed, so a few dozen
     // saturate the link (32 single-wave workgroups reach 40 GiB/s, 64 reach 50) and every further one only takes wave slots
     // from the sampling launches the copy runs under; and a single wavefront finds a slot whenever ONE sampling wavefront
@@ -2451,9 +2528,9 @@ int lmc_engine_copy_window_async(lmc_engine* e, const lmc_window_dst* dst, int64
         const long long lo = 0, hi = C;   // (all chains in one dispatch; the kernels take a chain range)
         hipStream_t st = cs;
         if (trace_dst) {
-            const long long rows = e->A.cap - e->A.trace_begin;
+            const long long rows = e->A.trace_rows;
             const long long row = n * d, sp = rows * d, dp_ = n_out * d;
-            const double* src = e->A.trace + lo * sp + (iter_begin - e->A.trace_begin) * d;
+            const double* src = e->A.trace + lo * sp + ((win.first_kept - e->A.trace_begin) / e->A.thin) * d;
             double* out = trace_dst + lo * dp_ + row0 * d;
             const dim3 grid(static_cast<unsigned>(hi - lo < per_grid ? hi - lo : per_grid));
             const bool v2 = row % 2 == 0 && sp % 2 == 0 && dp_ % 2 == 0 && (reinterpret_cast<uintptr_t>(src) % 16 == 0) &&
@@ -2467,8 +2544,8 @@ int lmc_engine_copy_window_async(lmc_engine* e, const lmc_window_dst* dst, int64
             long long blocks = (total + kWindowCopyThreads - 1) / kWindowCopyThreads;
             if (blocks > per_grid) blocks = per_grid;
             const int rc = launched(e, launch(window_gather_kernel, dim3(static_cast<unsigned>(blocks)), cblock, 0, st, e->A.stat_rec,
-                                              e->A.cap, static_cast<int>(lo), static_cast<int>(hi - lo), iter_begin, n_iters,
-                                              e->cfg.kind == LMC_KIND_HMC ? 1 : 0, W, n_out, row0));
+                                              e->A.cap, static_cast<int>(lo), static_cast<int>(hi - lo), win.first_kept, n,
+                                              e->cfg.kind == LMC_KIND_HMC ? 1 : 0, W, n_out, row0, stride));
             if (rc != LMC_OK) return rc;
         }
     }
@@ -2521,6 +2598,8 @@ int lmc_host_unregister(void* p) {
 void* lmc_engine_trace_device_ptr(lmc_engine* e) { return e ? e->A.trace : nullptr; }
 void* lmc_engine_stat_records_device_ptr(lmc_engine* e) { return e ? static_cast<void*>(e->A.stat_rec) : nullptr; }
 int64_t lmc_engine_trace_begin(lmc_engine* e) { return e ? e->A.trace_begin : 0; }
+int64_t lmc_engine_thin(lmc_engine* e) { return e ? e->thin : 1; }
+int64_t lmc_engine_trace_rows(lmc_engine* e) { return e && e->A.trace ? e->A.trace_rows : 0; }
 int64_t lmc_engine_capacity(lmc_engine* e) { return e ? e->A.cap : 0; }
 
 int lmc_engine_get_adapt_state(lmc_engine* e, float* var, double* dual_avg, int32_t* da_count, int32_t* n_samples) {

@@ -93,8 +93,10 @@ struct ChainArrays {
     double* scratch;      // [C][scratch_stride]
     long long scratch_stride;
     // outputs (row = iteration index relative to the engine's reserved capacity)
-    double* trace;        // [C][cap - trace_begin][d] or nullptr
+    double* trace;        // [C][trace_rows][d] or nullptr: row r holds the draw of iteration trace_begin + r * thin
     long long trace_begin; // first iteration whose draw is stored
+    long long trace_rows;  // ceil((cap - trace_begin) / thin)
+    long long thin;        // every thin-th draw from trace_begin on is stored (lmc_engine_reserve_thinned; 1 = all of them)
     StatRecord* stat_rec; // [C][cap]: one 64-byte record of sampler statistics per draw
     long long cap;
 };
@@ -122,6 +124,12 @@ struct SamplerParams {
     double jitter_lo, jitter_hi;
     int relay_mask;       // stop word: one chain in (relay_mask + 1) of a launch reads the host's word (stop_request_load)
     int mass_f64;         // QuadPotentialDiagAdapt(dtype="float64"): the adapted diagonal is NOT rounded to float32 (wide kernels)
+    // The draws this launch stores (lmc_engine.hip: set_launch_window -- the host knows the phase of the launch's first
+    // iteration): its iterations keep_first, keep_first + thin, ... (counted from iter_begin) go to the trace rows
+    // trace_row0, trace_row0 + 1, ... No trace, or nothing of this launch is kept: keep_first = INT_MAX.
+    int keep_first;
+    int thin;
+    long long trace_row0;
 };
 
 // ---- kernel arguments, re-read where they are used ---------------------------------------------------------------
@@ -1802,13 +1810,31 @@ __device__ __forceinline__ double stat_record_value(int tid, const TransitionOut
     const double ints = __hiloint2double(static_cast<int>(flags), out.n_leapfrog);
     return (tid == 7) ? ints : v;
 }
-// the two stores of a draw: the trace row and the 64-byte record (eight lanes, ONE store)
+// The trace row of a draw, -1 = the draw is not stored (thinning: every A.thin-th draw from A.trace_begin on is).
+// A launch is a contiguous run of iterations, so the sampling kernels neither divide nor take a remainder: `kept` counts
+// the draws the launch has stored so far (one wave-uniform scalar carried across the iterations), the next one to store is
+// iteration keep_first + kept * thin of the launch and goes to row trace_row0 + kept. With thin = 1 this is the old test
+// git >= trace_begin in another form.
+template <class PT>
+__device__ __forceinline__ long long launch_trace_row(const PT& P, int it, int& kept) {
+    if (it != P.keep_first + kept * P.thin) return -1;
+    return P.trace_row0 + kept++;
+}
+// The chains of a tick launch stand at different iterations (lmc_tick.hpp): the row follows from the chain's own iteration.
+// One division per COMPLETED iteration of a kernel that is HBM-bound and completes an iteration every several ticks.
+template <class CA>
+__device__ __forceinline__ long long chain_trace_row(const CA& A, long long git) {
+    if (A.trace == nullptr || git < A.trace_begin) return -1;
+    const long long rel = git - A.trace_begin, r = rel / A.thin;
+    return r * A.thin == rel ? r : -1;
+}
+// the two stores of a draw: the trace row `trow` (< 0: none) and the 64-byte record (eight lanes, ONE store)
 template <int NS, class CA>
-__device__ __forceinline__ void store_outputs(const CA& A, int c, int tid, long long git, const double (&q)[NS], double rec) {
+__device__ __forceinline__ void store_outputs(const CA& A, int c, int tid, long long git, long long trow, const double (&q)[NS], double rec) {
     const int d = A.d;
     const long long orow = static_cast<long long>(c) * A.cap + git;
-    if (A.trace != nullptr && git >= A.trace_begin) {
-        double* tr = A.trace + (static_cast<long long>(c) * (A.cap - A.trace_begin) + (git - A.trace_begin)) * d;
+    if (trow >= 0) {
+        double* tr = A.trace + (static_cast<long long>(c) * A.trace_rows + trow) * d;
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
             const int e = tid * NS + s;
@@ -1818,9 +1844,9 @@ __device__ __forceinline__ void store_outputs(const CA& A, int c, int tid, long 
     if (tid < 8) reinterpret_cast<double*>(A.stat_rec + orow)[tid] = rec;
 }
 template <int NS, class CA>
-__device__ __forceinline__ void write_outputs(const CA& A, int c, int tid, long long git, const double (&q)[NS],
+__device__ __forceinline__ void write_outputs(const CA& A, int c, int tid, long long git, long long trow, const double (&q)[NS],
                                               const TransitionOut& out, double step_now, double step_bar_now, bool tune) {
-    store_outputs<NS>(A, c, tid, git, q, stat_record_value(tid, out, step_now, step_bar_now, tune));
+    store_outputs<NS>(A, c, tid, git, trow, q, stat_record_value(tid, out, step_now, step_bar_now, tune));
 }
 
 // diagonal mass adaptation (quadpotential.py:231-245, :324-340): both Welford estimators take the draw, the
@@ -1996,6 +2022,7 @@ __global__ __launch_bounds__(64 * W, run_waves_per_simd(NS, W)) void run_kernel(
 #define LMC_PHASE(i)
 #endif
     const int n_iters = P0.n_iters;
+    int kept = 0;   // draws of this launch stored so far (launch_trace_row)
     for (int it = 0; it < n_iters; ++it) {
         // ---- region 1 of the arguments: iteration head (momentum draw, start state, step size, transition inputs)
         KSamplerParams& P = ka.P();
@@ -2116,10 +2143,10 @@ __global__ __launch_bounds__(64 * W, run_waves_per_simd(NS, W)) void run_kernel(
 
         if (A.mom_mean != nullptr && !tune) moments_update<NS>(A, tm, c, row, q);
         if constexpr (LMC_EARLY_STOP_CHECK != 0) {
-            store_outputs<NS>(A, c, tid, git, q, rec_value);
+            store_outputs<NS>(A, c, tid, git, launch_trace_row(P2, it, kept), q, rec_value);
             if (stop_now) break;
         } else {
-            write_outputs<NS>(A, c, tid, git, q, out, da.step_now, da.step_bar_now, tune);
+            write_outputs<NS>(A, c, tid, git, launch_trace_row(P2, it, kept), q, out, da.step_now, da.step_bar_now, tune);
             if (stop_requested(tm, stop_word, rng_bcast)) break;
         }
     }

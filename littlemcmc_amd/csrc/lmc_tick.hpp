@@ -502,7 +502,7 @@ __device__ __forceinline__ void tick_step(const ChainArrays& A, const TickArrays
         }
         ++iter_count;
         if (A.mom_mean != nullptr && !tune) moments_update<NS>(A, tm, c, row, q);
-        write_outputs<NS>(A, c, lane, git, q, out, da.step_now, da.step_bar_now, tune);
+        write_outputs<NS>(A, c, lane, git, chain_trace_row(A, git), q, out, da.step_now, da.step_bar_now, tune);
         vstore<NS>(A.q + row, q);
         if (lane == 0) {
             A.counters[c * kNumCounters + kCtMaxTreedepth] += ct_maxdepth;

@@ -445,6 +445,7 @@ __global__ __launch_bounds__(64 * W) void run_wide_kernel(ChainArrays A, DenseAr
     const bool momentum_f32 = P.momentum_f32 != 0;
     const bool mass_f32 = P.mass_f64 == 0;
 
+    int kept = 0;   // draws of this launch stored so far (launch_trace_row)
     for (int it = 0; it < P.n_iters; ++it) {
         const long long git = P.iter_begin + it;
         const bool tune = git < P.n_tune;
@@ -476,7 +477,7 @@ __global__ __launch_bounds__(64 * W) void run_wide_kernel(ChainArrays A, DenseAr
         ++iter_count;
         if (!tune) ++ct_after;
         if (A.mom_mean != nullptr && !tune) moments_update<NS>(A, tm, c, row, q);
-        write_outputs<NS>(A, c, tid, git, q, out, da.step_now, da.step_bar_now, tune);
+        write_outputs<NS>(A, c, tid, git, launch_trace_row(P, it, kept), q, out, da.step_now, da.step_bar_now, tune);
         if (stop_requested(tm, stop_word, bcast)) break;
     }
 

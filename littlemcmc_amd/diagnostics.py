@@ -352,8 +352,9 @@ class _DevicePtr:
 
 
 def trace_tensor(engine, n_draws=None):
-    """Zero-copy torch view [chains, capacity - trace_begin, dim] of the engine's draws in HBM (an EngineGroup: the list
-    of its engines' views, one per GPU -- summarize() takes it as it is). ``n_draws`` keeps the first n_draws draws of
+    """Zero-copy torch view [chains, trace_rows, dim] of the engine's draws in HBM (an EngineGroup: the list
+    of its engines' views, one per GPU -- summarize() takes it as it is): capacity - trace_begin rows, or, on a thinned
+    engine (reserve(thin=k)), the ceil((capacity - trace_begin) / k) kept draws. ``n_draws`` keeps the first n_draws rows of
     every chain only: the rows an interrupted run has actually written."""
     if hasattr(engine, "engines"):
         return [trace_tensor(e, n_draws) for e in engine.engines]
@@ -363,5 +364,5 @@ def trace_tensor(engine, n_draws=None):
     if not ptr:
         raise RuntimeError("the engine keeps no trace (reserve(keep_trace=False))")
     engine.synchronize()
-    shape = (engine.chains, engine.capacity - engine.trace_begin, engine.dim)
+    shape = (engine.chains, engine.trace_rows(), engine.dim)
     return torch.as_tensor(_DevicePtr(ptr, shape), device="cuda:%d" % engine.cfg.device)

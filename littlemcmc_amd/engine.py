@@ -13,6 +13,20 @@ from . import _abi
 DEFAULT_SDOT = "auto"
 
 
+def thin_window(first, n, lo, k):
+    """Which draws a window of iterations keeps under thinning -- the one statement of that arithmetic on the host
+    (the library's mirror is lmc_thin_window, which sets every launch's kernel arguments). Of the iterations
+    [first, first + n), a job that keeps ``lo, lo + k, lo + 2k, ...`` keeps ``first_kept, first_kept + k, ...``
+    (``n_kept`` of them) and ``first_kept`` is row ``first_row`` of the thinned arrays.
+    Returns (first_kept, n_kept, first_row); n_kept == 0: nothing of the window is kept."""
+    first, n, lo, k = int(first), int(n), int(lo), int(k)
+    if first < 0 or n < 0 or lo < 0 or k < 1:
+        raise ValueError("thin_window needs first, n, lo >= 0 and k >= 1 (got %r)" % ((first, n, lo, k),))
+    first_row = -(-(max(first, lo) - lo) // k)
+    first_kept = lo + first_row * k
+    return first_kept, max(-(-(first + n - first_kept) // k), 0), first_row
+
+
 class _TickView:
     """__cuda_array_interface__ shim over the engine's evaluation-point buffer (float64 [chains, dim])."""
 
@@ -120,10 +134,12 @@ class StreamedResults:
     next launch): ``trace[chains, n_out, dim]`` float64 and one ``[chains, n_out]`` array per statistic, already in the
     dtype of the reference's stats dict (the device converts), iteration ``first`` in row 0.
 
-    ``planes``: (name, kind, idx, as_, numpy dtype) with kind / as_ the LMC_PLANE_* / LMC_AS_* of include/lmc_hip.h."""
+    ``planes``: (name, kind, idx, as_, numpy dtype) with kind / as_ the LMC_PLANE_* / LMC_AS_* of include/lmc_hip.h.
+    ``thin`` = k: the ``n_out`` rows hold the iterations ``first, first + k, first + 2k, ...`` (a thinned job)."""
 
     def __init__(self, chains, n_out, first, dim, planes, keep_trace=True, pinned=True, lib=None, copy_workgroups=0, direct=False,
-                 register=True):
+                 register=True, thin=1):
+        self.thin = int(thin)
         self.direct = bool(direct)      # the sampling kernel writes ``trace`` itself (Engine.attach_trace): windows carry statistics only
         self.copy_workgroups = int(copy_workgroups)     # lmc_window_dst.copy_workgroups (0 = the library's default)
         self.chains, self.n_out, self.first, self.dim = int(chains), int(n_out), int(first), int(dim)
@@ -290,6 +306,7 @@ class Engine:
         self.capacity = 0
         self.keep_trace = False
         self.trace_begin = 0
+        self.thin = 1
         self.wide = bool(self._lib.lmc_engine_uses_general_kernels(self._h))   # include/lmc_hip.h: "Which kernels an engine runs"
 
     def kernel_shape(self):
@@ -371,21 +388,30 @@ class Engine:
                                                           int(count)))
 
     # ---- sampling -----------------------------------------------------------------------------------
-    def reserve(self, capacity, keep_trace=True, trace_begin=0):
-        """Output storage for ``capacity`` iterations; draws kept for iterations >= trace_begin."""
+    def reserve(self, capacity, keep_trace=True, trace_begin=0, thin=1):
+        """Output storage for ``capacity`` iterations; draws kept for the iterations trace_begin, trace_begin + thin, ...
+        (lmc_engine_reserve_thinned: the discarded draws are never stored; the statistic records stay one per iteration)."""
         tb = int(trace_begin) if keep_trace else -1
-        self._check(self._lib.lmc_engine_reserve(self._h, int(capacity), tb))
+        self._check(self._lib.lmc_engine_reserve_thinned(self._h, int(capacity), tb, int(thin)))
         self.capacity = int(capacity)
         self.keep_trace = bool(keep_trace) and tb < capacity
         self.trace_begin = max(tb, 0)
+        self.thin = int(thin)
         self._trace_out = None           # (reserve detached it: the engine writes its own trace, or none)
 
+    def trace_rows(self, trace_begin=None):
+        """Rows per chain of the trace: the kept iterations in [trace_begin, capacity) (default: the engine's own trace_begin;
+        0 where no trace is kept)."""
+        if trace_begin is None:
+            return int(self._lib.lmc_engine_trace_rows(self._h))
+        return thin_window(trace_begin, self.capacity - int(trace_begin), trace_begin, self.thin)[1]
+
     def attach_trace(self, out, trace_begin):
-        """Where the draws of iterations >= trace_begin go, after reserve(keep_trace=False): ``out`` = a device-accessible
-        [chains, capacity - trace_begin, dim] float64 array (pinned_empty) the sampling kernel writes directly, or None = a
-        trace in HBM (include/lmc_hip.h: lmc_engine_attach_trace)."""
+        """Where the draws of the iterations trace_begin, trace_begin + thin, ... go, after reserve(keep_trace=False): ``out`` =
+        a device-accessible [chains, trace_rows(trace_begin), dim] float64 array (pinned_empty) the sampling kernel writes
+        directly, or None = a trace in HBM (include/lmc_hip.h: lmc_engine_attach_trace)."""
         if out is not None:
-            assert out.shape == (self.chains, self.capacity - int(trace_begin), self.dim) and out.dtype == np.float64 and out.flags["C_CONTIGUOUS"]
+            assert out.shape == (self.chains, self.trace_rows(trace_begin), self.dim) and out.dtype == np.float64 and out.flags["C_CONTIGUOUS"]
         self._check(self._lib.lmc_engine_attach_trace(self._h, None if out is None else C.c_void_p(out.ctypes.data), int(trace_begin)))
         self._trace_out = out            # (kept alive for as long as the engine may write it)
         self.keep_trace, self.trace_begin = True, int(trace_begin)
@@ -526,9 +552,10 @@ class Engine:
             self.set_stream(None)
 
     def trace(self, iter_begin=None, n_iters=None):
+        """The kept draws among the iterations [iter_begin, iter_begin + n_iters) (default: all of them), in order."""
         iter_begin = self.trace_begin if iter_begin is None else iter_begin
         n = self.capacity - iter_begin if n_iters is None else n_iters
-        out = np.empty((self.chains, n, self.dim))
+        out = np.empty((self.chains, thin_window(iter_begin, n, self.trace_begin, self.thin)[1], self.dim))
         self._check(self._lib.lmc_engine_get_trace(self._h, _abi.ptr(out), int(iter_begin), int(n)))
         return out
 
@@ -554,8 +581,9 @@ class Engine:
     def copy_window_async(self, out, iter_begin, n_iters, chain_lo=0):
         """Enqueue the device->host copy of iterations [iter_begin, iter_begin + n_iters) of every chain into the final
         arrays of ``out`` (a StreamedResults; this engine's chains start at its row ``chain_lo``), ordered after the launches
-        enqueued so far, asynchronous to the host."""
-        self._check(self._lib.lmc_engine_copy_window_async(self._h, C.byref(out.window_dst(self, chain_lo)), int(iter_begin), int(n_iters)))
+        enqueued so far, asynchronous to the host. Of the window, the iterations ``out`` keeps (``out.thin``) are written."""
+        self._check(self._lib.lmc_engine_copy_window_strided_async(self._h, C.byref(out.window_dst(self, chain_lo)), int(iter_begin),
+                                                                   int(n_iters), int(out.thin)))
 
     def copy_wait(self):
         self._check(self._lib.lmc_engine_copy_wait(self._h))
@@ -836,7 +864,7 @@ class EngineGroup:
     def attach_trace(self, out, trace_begin):
         for e, (lo, hi) in zip(self.engines, self.blocks):
             e.attach_trace(None if out is None else out[lo:hi], trace_begin)
-        self.keep_trace, self.trace_begin = self.engines[0].keep_trace, self.engines[0].trace_begin
+        self.keep_trace, self.trace_begin, self.thin = self.engines[0].keep_trace, self.engines[0].trace_begin, self.engines[0].thin
 
     def copy_wait(self):
         self._each("copy_wait")
@@ -882,10 +910,14 @@ class EngineGroup:
             e.set_step_sizes(a[lo:hi])
 
     # ---- sampling ---------------------------------------------------------------------------------------------------
-    def reserve(self, capacity, keep_trace=True, trace_begin=0):
-        self._each("reserve", capacity, keep_trace=keep_trace, trace_begin=trace_begin)
-        self.capacity, self.keep_trace, self.trace_begin = (self.engines[0].capacity, self.engines[0].keep_trace,
-                                                            self.engines[0].trace_begin)
+    def reserve(self, capacity, keep_trace=True, trace_begin=0, thin=1):
+        """One ``thin`` for all member engines; capacity / keep_trace / trace_begin / thin read as on one Engine."""
+        self._each("reserve", capacity, keep_trace=keep_trace, trace_begin=trace_begin, thin=thin)
+        self.capacity, self.keep_trace, self.trace_begin, self.thin = (self.engines[0].capacity, self.engines[0].keep_trace,
+                                                                       self.engines[0].trace_begin, self.engines[0].thin)
+
+    def trace_rows(self, trace_begin=None):
+        return self.engines[0].trace_rows(trace_begin)
 
     def run(self, n_tune, iter_begin, n_iters):
         """Asynchronous on every device (fused kernels): the launch is enqueued everywhere before anyone waits."""

@@ -16,12 +16,28 @@ import numpy as np
 
 from . import _abi
 from .base_hmc import raise_for_status
+from .engine import thin_window
 from .nuts import NUTS
 from .quadpotential import SNAPSHOTS_PER_WINDOW, QuadPotentialDiagAdapt, QuadPotentialFullAdapt, QuadPotentialFullPooled
 from .targets import require_device_target
 
 _log = logging.getLogger("littlemcmc_amd")
 _STREAM_MIN_BYTES = 8 << 20   # results smaller than this are copied when the job is over (stream_results=True only: an explicit mode is honoured)
+
+
+def _check_thin(thin):
+    """``thin`` of sample(): an integer >= 1 (bool is not one here: ``thin=True`` is a mistake, not 1)."""
+    if isinstance(thin, (bool, np.bool_)) or not isinstance(thin, (int, np.integer)) or thin < 1:
+        raise ValueError("thin must be an integer >= 1 (got %r)" % (thin,))
+    return int(thin)
+
+
+def _thin_kw(thin):
+    """``thin`` as a keyword for the engine-side calls of a job (reserve, _ResultStreamer, StreamedResults): it goes along only
+    where the job is thinned, so an unthinned job calls them with the arguments it always did and engine-like objects
+    written against that signature keep working. (Below these calls there is one path: Engine.reserve and
+    Engine.copy_window_async always enter the library through the thinned / strided entry points, with 1.)"""
+    return {"thin": thin} if thin != 1 else {}
 
 
 def _derive_seeds(random_seed, chains):
@@ -105,9 +121,11 @@ class _ResultStreamer:
       ends); ``direct=False`` -- the trace stays in HBM and every launch's window is copied under the following launches.
     * statistics (82 bytes per draw): the window of every launch is gathered out of the per-draw records, converted to the
       reference's dtypes on the device and written into the returned arrays under the following launches
-      (Engine.copy_window_async). Windows that come before the arrays exist wait in a list."""
+      (Engine.copy_window_async). Windows that come before the arrays exist wait in a list.
+    * a thinned job (``thin`` = k): the arrays have the ``n_out`` kept rows, iteration ``first + r * k`` in row r; the kernel
+      stores only those draws and every window's copy writes only those statistics (lmc_engine_copy_window_strided_async)."""
 
-    def __init__(self, eng, chains, n_out, first, dim, planes, direct):
+    def __init__(self, eng, chains, n_out, first, dim, planes, direct, thin=1):
         import threading
 
         self.eng, self.first, self.out, self.err, self.waiting = eng, int(first), None, None, []
@@ -123,7 +141,7 @@ class _ResultStreamer:
             was_enabled = gc.isenabled()
             gc.disable()
             try:
-                self.out = StreamedResults(chains, n_out, first, dim, planes, direct=direct, register=False)
+                self.out = StreamedResults(chains, n_out, first, dim, planes, direct=direct, register=False, **_thin_kw(thin))
             except BaseException as err:     # the host cannot allocate that much: the draws are copied after the job instead
                 self.err = err
             finally:
@@ -508,17 +526,19 @@ def _launch_schedule(n_total, launch_iters, slots, per_dev, wide, external):
     return per_launch
 
 
-def _collect_results(step, eng, streamed, lo, n_done, chains, model_ndim):
-    """(trace[chains, n, ndim], stats[name][chains, n, 1]) of the iterations [lo, n_done): views of the streamed arrays
-    (an interrupted job returns the iterations every chain completed: a prefix of them), a copy from the engine, or empty."""
-    n_out = max(n_done - lo, 0)
+def _collect_results(step, eng, streamed, lo, n_done, chains, model_ndim, thin=1):
+    """(trace[chains, n, ndim], stats[name][chains, n, 1]) of the kept iterations lo, lo + thin, ... below n_done: views of
+    the streamed arrays (an interrupted job returns the iterations every chain completed: a prefix of the kept rows), a copy
+    from the engine, or empty."""
+    n_iter = max(n_done - lo, 0)
+    n_out = thin_window(lo, n_iter, lo, thin)[1]
     dtypes = step.stats_dtypes[0].items()
     if n_out > 0 and streamed is not None:
         trace = streamed.trace if n_out == streamed.n_out else streamed.trace[:, :n_out]
         return trace, {name: streamed.stats[name][:, :n_out, None].astype(dtype, copy=False) for name, dtype in dtypes}
-    if n_out > 0:
-        trace, raw = eng.trace(lo, n_out), step._stats_from_engine(eng, lo, n_out)
-        return trace, {name: raw[name][:, :, None].astype(dtype) for name, dtype in dtypes}
+    if n_out > 0:   # (the records on the device are one per iteration: the kept ones are picked here)
+        trace, raw = eng.trace(lo, n_iter), step._stats_from_engine(eng, lo, n_iter)
+        return trace, {name: raw[name][:, ::thin, None].astype(dtype) for name, dtype in dtypes}
     return np.zeros((chains, 0, model_ndim)), {name: np.zeros((chains, 0, 1), dtype=dtype) for name, dtype in dtypes}
 
 
@@ -544,7 +564,7 @@ def _write_back_step_state(step, eng, tune, n_total, n_done, interrupted, chains
 def sample(logp_dlogp_func, model_ndim=None, draws=1000, tune=1000, step=None, init="auto", chains=None,
            cores=None, start=None, progressbar=True, random_seed=None, discard_tuned_samples=True,
            chain_idx=0, callback=None, mp_ctx=None, pickle_backend="pickle", size=None, device=None, devices=None,
-           launch_iters=None, return_engine=False, keep_moments=False, stream_results=True, **kwargs):
+           launch_iters=None, return_engine=False, keep_moments=False, stream_results=True, thin=1, **kwargs):
     """Draw samples with many chains on the MI355X(s) of this node (reference signature: sampling.py:35-53).
 
     Where the reference fans its chains out over ``cores`` worker processes (sampling.py:124-129,186-201), this fans
@@ -557,7 +577,7 @@ def sample(logp_dlogp_func, model_ndim=None, draws=1000, tune=1000, step=None, i
     (iterations per kernel launch; default: the whole run in at most a few launches),
     ``return_engine`` (also return the live Engine -- an EngineGroup on several GPUs -- e.g. to read device pointers),
     ``keep_moments`` (the kernel also keeps every chain's running mean / M2 of the post-warm-up draws:
-    ``Engine.moments()``). ``callback(trace=None, draw=JobProgress)`` is called from the wait loop as the job advances
+    ``Engine.moments()``), ``thin`` (keep every k-th draw: below). ``callback(trace=None, draw=JobProgress)`` is called from the wait loop as the job advances
     and may raise KeyboardInterrupt to stop it (sampling.py:272-277 of the reference); ``mp_ctx`` and
     ``pickle_backend`` are accepted and ignored (no worker processes). ``stream_results``: True / "direct" (default) --
     the returned arrays are page-locked host memory, the sampling kernel writes every draw straight into the returned trace
@@ -565,7 +585,14 @@ def sample(logp_dlogp_func, model_ndim=None, draws=1000, tune=1000, step=None, i
     (lmc_engine_copy_window_async); "windows" -- the trace stays in HBM and is copied window by window like the statistics;
     False -- everything stays on the device until the job is over, then one blocking copy. The same arrays bit for bit
     (test_streamed_results_equal_the_copy_after_the_job).
+
+    ``thin=k`` (an integer >= 1) keeps every k-th of the returned iterations: with ``lo = tune if discard_tuned_samples
+    else 0`` the iterations ``lo, lo + k, lo + 2k, ...`` -- bit for bit ``trace[:, ::k]`` and ``stats[name][:, ::k]`` of the
+    same job with ``thin=1``, in ``ceil((tune + draws - lo) / k)`` rows. The discarded draws are never stored, in HBM or
+    over the host link (the sampling kernel skips their store), and the returned arrays are k times smaller. Only the
+    outputs change: tuning, ``keep_moments``, the counters and warnings see every iteration.
     """
+    thin = _check_thin(thin)
     if model_ndim is None:
         model_ndim = size if size is not None else getattr(logp_dlogp_func, "d", None)
     target = require_device_target(logp_dlogp_func, model_ndim)
@@ -592,6 +619,7 @@ def sample(logp_dlogp_func, model_ndim=None, draws=1000, tune=1000, step=None, i
 
     tune, n_total = int(tune), int(tune) + int(draws)
     lo = tune if discard_tuned_samples else 0   # sampling.py:473-476
+    n_rows = thin_window(lo, max(n_total - lo, 0), lo, thin)[1]   # rows of the returned arrays: the iterations lo, lo + thin, ...
 
     def _probe_slots():   # resident wavefront slots of this job's sampling kernel on one GPU (a one-chain engine knows)
         if external:
@@ -625,14 +653,14 @@ def sample(logp_dlogp_func, model_ndim=None, draws=1000, tune=1000, step=None, i
         # kernel writes the draws straight into them ("direct") and every launch's statistics are copied under the launches
         # that follow (_ResultStreamer).
         mode = _result_mode(stream_results, return_engine=return_engine, host_rand=host_rand, external=external,
-                            has_planes=hasattr(step, "_result_planes"), chains=chains, n_out=n_total - lo, model_ndim=model_ndim)
-        eng.reserve(max(n_total, 1), keep_trace=mode != "direct", trace_begin=min(lo, max(n_total - 1, 0)))
+                            has_planes=hasattr(step, "_result_planes"), chains=chains, n_out=n_rows, model_ndim=model_ndim)
+        eng.reserve(max(n_total, 1), keep_trace=mode != "direct", trace_begin=min(lo, max(n_total - 1, 0)), **_thin_kw(thin))
         slots = None if launch_iters else eng.resident_chains()
         wide = getattr(getattr(eng, "engines", [eng])[0], "wide", False)
         per_launch = _launch_schedule(n_total, launch_iters, slots, -(-chains // len(devs)), wide, external)
         streamer = None
         if mode is not None:
-            streamer = _ResultStreamer(eng, chains, n_total - lo, lo, model_ndim, step._result_planes(), direct=mode == "direct")
+            streamer = _ResultStreamer(eng, chains, n_rows, lo, model_ndim, step._result_planes(), direct=mode == "direct", **_thin_kw(thin))
         try:
             if host_rand:
                 n_done, interrupted = _run_job_host_step_rand(eng, step, tune, n_total, progressbar, callback)
@@ -652,7 +680,7 @@ def sample(logp_dlogp_func, model_ndim=None, draws=1000, tune=1000, step=None, i
             raise
         streamed = streamer.finish() if streamer is not None else None
         raise_for_status(eng.status())
-        trace, stats = _collect_results(step, eng, streamed, lo, n_done, chains, model_ndim)
+        trace, stats = _collect_results(step, eng, streamed, lo, n_done, chains, model_ndim, thin)
         _write_back_step_state(step, eng, tune, n_total, n_done, interrupted, chains)
     except BaseException:   # KeyboardInterrupt / SystemExit included: never leak the engine (its HBM, its streams)
         eng.close()

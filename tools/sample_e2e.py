@@ -4,7 +4,10 @@ as numpy arrays (sampling.py:207-222 of the reference), with the results streame
 runs (the default) and copied in one piece after it (stream_results=False), next to the kernel-only time of the same job
 (draws left in HBM). "hidden" = 1 - (streamed - kernel) / (after - kernel): the share of the copy-out that no longer shows.
 
-    python tools/sample_e2e.py [c2|c3|std128] [chains] [tune] [draws] [repeats]
+    python tools/sample_e2e.py [c2|c3|std128] [chains] [tune] [draws] [repeats] [--thin K]
+
+``--thin K``: the same with sample(thin=K) -- every K-th draw kept -- and, per run, the size of the arrays the call returned
+and the time to free them (dropping the last reference unpins them).
 """
 import os
 import sys
@@ -16,6 +19,11 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import littlemcmc_amd as lmc  # noqa: E402
 from littlemcmc_amd import _abi  # noqa: E402
 
+THIN = 1
+if "--thin" in sys.argv:
+    i = sys.argv.index("--thin")
+    THIN = int(sys.argv[i + 1])
+    del sys.argv[i:i + 2]
 cfg = sys.argv[1] if len(sys.argv) > 1 else "c3"
 shape = {"c2": ("std_normal", 64, 4096), "c3": ("ar1", 128, 65536), "std128": ("std_normal", 128, 65536)}[cfg]
 chains = int(sys.argv[2]) if len(sys.argv) > 2 else shape[2]
@@ -25,8 +33,8 @@ reps = int(sys.argv[5]) if len(sys.argv) > 5 else 2
 d = shape[1]
 tgt = lmc.targets.AR1(d, 0.9) if shape[0] == "ar1" else lmc.targets.StdNormal(d)
 SEED = 20260928
-out_gib = chains * draws * (d * 8 + 82) / 2.0 ** 30
-print("%s: %d chains x d=%d, tune %d + draws %d; the call returns %.2f GiB (trace + 11 statistics)" % (cfg, chains, d, tune, draws, out_gib))
+out_gib = chains * -(-draws // THIN) * (d * 8 + 82) / 2.0 ** 30
+print("%s: %d chains x d=%d, tune %d + draws %d, thin %d; the call returns %.2f GiB (trace + 11 statistics)" % (cfg, chains, d, tune, draws, THIN, out_gib))
 
 
 def kernel_only():
@@ -40,7 +48,7 @@ def kernel_only():
         eng.seed(seeds)
         eng.set_position(start)
         eng.reset_tuning()
-        eng.reserve(tune + draws, keep_trace=True, trace_begin=tune)
+        eng.reserve(tune + draws, keep_trace=True, trace_begin=tune, thin=THIN)
         per = sampling._launch_schedule(tune + draws, None, eng.resident_chains(), chains, eng.wide, False)
         eng.synchronize()
         t0 = time.perf_counter()
@@ -55,11 +63,17 @@ def kernel_only():
 def call(stream):
     t0 = time.perf_counter()
     trace, stats = lmc.sample(tgt, d, draws=draws, tune=tune, chains=chains, random_seed=SEED, progressbar=False,
-                              stream_results=stream)
+                              stream_results=stream, thin=THIN)
     dt = time.perf_counter() - t0
     chk = float(trace[::max(1, chains // 64), -1].sum()) + float(stats["tree_size"][::max(1, chains // 64)].sum())
+    nbytes = trace.nbytes + sum(v.nbytes for v in stats.values())
+    t1 = time.perf_counter()
     del trace, stats
+    FREED.append((stream, nbytes, time.perf_counter() - t1))
     return dt, chk
+
+
+FREED = []   # (mode, bytes returned, seconds to free them) per call
 
 
 kernel_only()   # warm-up: code objects, allocator, first pinned allocation
@@ -73,6 +87,7 @@ for r in range(reps):
     assert c1 == c2 == c3, (c1, c2, c3)
     hidden = 1.0 - (ts - tk) / max(ta - tk, 1e-9)
     rows.append((tk, ts, ta, hidden))
+    print("run %d: returned %s" % (r, " | ".join("%s %.3f GiB freed in %.3f s" % (str(m), b / 2.0 ** 30, t) for m, b, t in FREED[-3:])))
     print("run %d: kernel only %.3f s (%.3e leapfrog-steps/s) | sample() direct %.3f s | windows %.3f s | copy-after %.3f s | copy-out %.3f s -> %.3f s (direct; windows %.3f s), %.0f %% hidden"
           % (r, tk, leaps / tk, ts, tw, ta, ta - tk, ts - tk, tw - tk, 100 * hidden))
 best = min(rows, key=lambda x: x[1])
