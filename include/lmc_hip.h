@@ -238,6 +238,30 @@ int lmc_engine_synchronize(lmc_engine* e);
 
 /* ---- plug-in parameters: the closure of the user's logp_dlogp_func (integration.py:40) ----------- */
 int lmc_engine_set_target_params(lmc_engine* e, const double* params, int64_t n);
+/* Per-group parameters (additive within ABI 9): many posteriors in one job. `params` is a host table [n_groups][n_per_group],
+ * row-major; chain j of the JOB evaluates the density on row j / chains_per_group, and this engine's chain c is chain
+ * first_chain + c of the job (an engine holds one contiguous block of a job's chains; the block may begin and end inside a
+ * group). The kernels choose the row once per launch, where they call the functor's init(Team&, const double* params, int d):
+ * no functor changes, a run-time compiled one included, and chain c computes bit for bit what it computes in an engine
+ * whose lmc_engine_set_target_params() got that row. On the device the rows start 16-byte aligned (the distance between rows
+ * is n_per_group rounded up to an even number of doubles, the pad is zero).
+ * Refused with LMC_ERR_INVALID before any HIP call: n_groups < 1, chains_per_group < 1, first_chain < 0, n_per_group < 0,
+ * a row length the family does not take (as lmc_engine_set_target_params: diag_gaussian dim, ar1 3, normal1d 2), and a
+ * table too short for the engine's chains: (first_chain + chains - 1) / chains_per_group >= n_groups.
+ * lmc_engine_set_target_params() is the case of one row for all chains; calling it again returns the engine to that.
+ * lmc_engine_target_groups(): what the engine holds (NULL pointers are skipped); an engine without a table reports
+ * n_groups 1, n_per_group n, first_chain 0, chains_per_group chains. */
+int lmc_engine_set_target_params_grouped(lmc_engine* e, const double* params, int64_t n_groups, int64_t n_per_group,
+                                         int64_t first_chain, int64_t chains_per_group);
+int lmc_engine_target_groups(lmc_engine* e, int64_t* n_groups, int64_t* n_per_group, int64_t* first_chain, int64_t* chains_per_group);
+/* The row arithmetic as a pure function (no engine, no GPU): *row = (first_chain + chain) / chains_per_group for chain `chain`
+ * of an engine whose chain 0 is the job's chain first_chain. chain, first_chain in [0, 2^31), chains_per_group in [1, 2^31),
+ * else LMC_ERR_INVALID. */
+int lmc_target_param_row(int64_t chain, int64_t first_chain, int64_t chains_per_group, int64_t* row);
+/* Everything lmc_engine_set_target_params_grouped() refuses, for an engine of `chains` chains of dimension `dim` and family
+ * `target_family`, as a pure function (no engine, no GPU): the setter calls exactly this before its first HIP call. */
+int lmc_target_groups_check(int32_t target_family, int32_t dim, int32_t chains, int64_t n_groups, int64_t n_per_group,
+                            int64_t first_chain, int64_t chains_per_group);
 
 /* ---- potential: QuadPotentialDiagAdapt(n, initial_mean, initial_diag, initial_weight)
  *      (quadpotential.py:151-204) or QuadPotentialDiag(v) (quadpotential.py:349-365).

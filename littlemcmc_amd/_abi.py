@@ -112,6 +112,11 @@ _SIGNATURES = {
     "lmc_engine_set_stream": (C.c_int, [_P, _P]),
     "lmc_engine_synchronize": (C.c_int, [_P]),
     "lmc_engine_set_target_params": (C.c_int, [_P, _P, C.c_int64]),
+    "lmc_engine_set_target_params_grouped": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
+    "lmc_engine_target_groups": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                           C.POINTER(C.c_int64)]),
+    "lmc_target_param_row": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
+    "lmc_target_groups_check": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
     "lmc_engine_set_potential": (C.c_int, [_P, _P, _P, C.c_double, C.c_int32]),
     "lmc_engine_set_dense_potential": (C.c_int, [_P, _P, _P, C.c_double, C.c_int32, C.c_double, C.c_int32]),
     "lmc_engine_get_dense_state": (C.c_int, [_P, C.POINTER(DenseState)]),

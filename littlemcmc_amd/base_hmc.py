@@ -125,11 +125,13 @@ class BaseHMC:
             mass_dtype=getattr(self.potential, "dtype", "float32") if self.potential._engine_kind in ("diag_adapt", "diag", "full_adapt") else "float32",
         )
 
-    def _make_engine(self, chains, device=0):
-        """A fresh engine for ``chains`` chains configured like this step (used by sample())."""
+    def _make_engine(self, chains, device=0, first_chain=0, chains_per_group=None):
+        """A fresh engine for ``chains`` chains configured like this step (used by sample()). ``first_chain`` /
+        ``chains_per_group``: where the engine's chains lie in the groups of a ``targets.Batched`` (Engine)."""
         from .engine import Engine
 
-        eng = Engine(self._logp_dlogp_func, chains=chains, device=device, **self._engine_kwargs())
+        eng = Engine(self._logp_dlogp_func, chains=chains, device=device, first_chain=first_chain,
+                     chains_per_group=chains_per_group, **self._engine_kwargs())
         self.potential._push_initial(eng)
         if isinstance(self._step_rand, StepRandUniform):
             eng.set_step_jitter(self._step_rand.lo, self._step_rand.hi)
@@ -147,6 +149,9 @@ class BaseHMC:
 
     def _engine(self):
         if self._eng1 is None:
+            if getattr(self._logp_dlogp_func, "groups", None) is not None:
+                raise ValueError("a step on a targets.Batched has no single posterior to take one step on: use batched[g] "
+                                 "(the target of group g) for astep-style calls")
             self._eng1 = self._make_engine(1)
             self.potential._bind(self._eng1)
             self._eng1.reserve(1, keep_trace=False)

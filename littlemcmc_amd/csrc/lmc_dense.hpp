@@ -466,7 +466,7 @@ __device__ __forceinline__ void dense_run_chain(const ChainArrays& A, const Dens
     Team<1> tm{nullptr, 0};
     const int tid = tm.tid();
     TargetT<NS> tgt;
-    tgt.init(tm, tparams, d);
+    tgt.init(tm, target_param_row(tparams, A.tparam_stride, A.tparam_first, A.tparam_group, c), d);
     lds_double* xop = (lds_double*)lds;
     double q[NS];
     vload<NS>(A.q + row, q);
@@ -664,7 +664,7 @@ __global__ __launch_bounds__(64) void dense_trajectory_kernel(ChainArrays A, Den
     const int d = A.d, dpad = A.dpad;
     Team<1> tm{nullptr, 0};
     TargetT<NS> tgt;
-    tgt.init(tm, tparams, d);
+    tgt.init(tm, target_param_row(tparams, A.tparam_stride, A.tparam_first, A.tparam_group, c), d);
     const MatT* M = static_cast<const MatT*>(D.covT) + static_cast<long long>(c) * D.mat_stride;
     DenseMat<MatT> mm{M, nullptr, 0, d, dpad};
     double q[NS], p[NS], g[NS], v[NS], w[NS], vs[NS];

@@ -374,7 +374,8 @@ struct lmc_engine {
     bool main_dirty = true;     // work enqueued on the main stream that the sub-streams have not been ordered after
     ChainArrays A;
     double* tparams = nullptr;
-    int64_t n_tparams = 0;
+    int64_t n_tparams = 0;    // doubles per row of the target's parameter table
+    int64_t n_tgroups = 1;    // its rows (1: one row for all chains)
     double* init_mean = nullptr;   // [C][dpad]
     float* init_diag = nullptr;    // [C][dpad]
     double init_weight = 10.0;
@@ -1062,6 +1063,7 @@ int lmc_engine_create(const lmc_config* cfg, lmc_engine** out) {
     std::memset(&A, 0, sizeof(A));
     A.chains = cfg->chains;
     A.thin = 1;
+    A.tparam_group = cfg->chains;   // one parameter row for all chains (stride 0) until a table is uploaded
     A.d = cfg->dim;
     A.dpad = e->dpad;
     int rc = LMC_OK;
@@ -1451,23 +1453,112 @@ int lmc_engine_synchronize(lmc_engine* e) {
     return LMC_OK;
 }
 
-int lmc_engine_set_target_params(lmc_engine* e, const double* params, int64_t n) {
-    if (!e || n < 0 || (n > 0 && !params)) return fail(e, LMC_ERR_INVALID, "bad target params");
-    HIP_TRY(e, hipSetDevice(e->cfg.device));
-    if (e->cfg.target_family == LMC_TARGET_DIAG_GAUSSIAN && n != e->cfg.dim)
-        return fail(e, LMC_ERR_INVALID, "diag_gaussian needs %d precisions, got %lld", e->cfg.dim, (long long)n);
-    if (e->cfg.target_family == LMC_TARGET_AR1 && n != 3)
+// ---- target parameters: one row for all chains, or a table with one row per group of chains ---------------------------
+// Chain j of the JOB is in group j / chains_per_group; this engine's chain c is chain first_chain + c of the job (an engine
+// holds one contiguous block of a job's chains). The kernels choose the row where they call the functor's init()
+// (lmc_targets.hpp: target_param_row) from ChainArrays::tparam_*.
+int lmc_target_param_row(int64_t chain, int64_t first_chain, int64_t chains_per_group, int64_t* row) {
+    const int64_t lim = int64_t(1) << 31;
+    if (chain < 0 || first_chain < 0 || chains_per_group < 1 || chain >= lim || first_chain >= lim || chains_per_group >= lim)
+        return fail(nullptr, LMC_ERR_INVALID, "target_param_row: chain, first_chain in [0, 2^31) and chains_per_group in [1, 2^31)");
+    if (row) *row = (first_chain + chain) / chains_per_group;
+    return LMC_OK;
+}
+
+// the length a family's functor reads (lmc_targets.hpp), checked per row
+static int check_target_row(lmc_engine* e, int family, int dim, int64_t n) {
+    if (family == LMC_TARGET_DIAG_GAUSSIAN && n != dim)
+        return fail(e, LMC_ERR_INVALID, "diag_gaussian needs %d precisions, got %lld", dim, (long long)n);
+    if (family == LMC_TARGET_AR1 && n != 3)
         return fail(e, LMC_ERR_INVALID, "ar1 needs params {c_end, c_mid, off}");
-    if (e->cfg.target_family == LMC_TARGET_NORMAL1D && n != 2)
+    if (family == LMC_TARGET_NORMAL1D && n != 2)
         return fail(e, LMC_ERR_INVALID, "normal1d needs params {loc, scale}");
+    return LMC_OK;
+}
+
+// what can be said about a table's shape without an engine ...
+static int check_target_group_args(lmc_engine* e, int64_t n_groups, int64_t n_per_group, int64_t first_chain, int64_t chains_per_group) {
+    if (n_groups < 1) return fail(e, LMC_ERR_INVALID, "target groups: n_groups must be >= 1 (got %lld)", (long long)n_groups);
+    if (chains_per_group < 1)
+        return fail(e, LMC_ERR_INVALID, "target groups: chains_per_group must be >= 1 (got %lld)", (long long)chains_per_group);
+    if (first_chain < 0) return fail(e, LMC_ERR_INVALID, "target groups: first_chain must be >= 0 (got %lld)", (long long)first_chain);
+    if (n_per_group < 0) return fail(e, LMC_ERR_INVALID, "target groups: n_per_group must be >= 0 (got %lld)", (long long)n_per_group);
+    return LMC_OK;
+}
+// ... and everything the grouped setter refuses, before any HIP call
+static int check_target_groups(lmc_engine* e, int family, int dim, int chains, int64_t n_groups, int64_t n_per_group,
+                               int64_t first_chain, int64_t chains_per_group) {
+    const int64_t lim = int64_t(1) << 31;
+    const int rc = check_target_group_args(e, n_groups, n_per_group, first_chain, chains_per_group);
+    if (rc != LMC_OK) return rc;
+    if (chains < 1 || dim < 1) return fail(e, LMC_ERR_INVALID, "chains and dim must be >= 1");
+    if (chains_per_group >= lim || first_chain + chains > lim - 1 || n_per_group >= lim - 1 ||
+        n_groups > (int64_t(1) << 40) / (n_per_group + 2))
+        return fail(e, LMC_ERR_INVALID, "target groups: the table or the job's chain indices are beyond 32-bit indexing");
+    const int64_t last_row = (first_chain + chains - 1) / chains_per_group;
+    if (last_row >= n_groups)
+        return fail(e, LMC_ERR_INVALID, "target groups: chain %lld of the job reads row %lld of a table of %lld rows",
+                    (long long)(first_chain + chains - 1), (long long)last_row, (long long)n_groups);
+    return check_target_row(e, family, dim, n_per_group);
+}
+
+int lmc_target_groups_check(int32_t target_family, int32_t dim, int32_t chains, int64_t n_groups, int64_t n_per_group,
+                            int64_t first_chain, int64_t chains_per_group) {
+    return check_target_groups(nullptr, target_family, dim, chains, n_groups, n_per_group, first_chain, chains_per_group);
+}
+
+// rows start 16-byte aligned: the distance between rows is rounded up to an even number of doubles (the pad is zero)
+static int64_t target_row_stride(int64_t n_per_group) { return (n_per_group + 1) / 2 * 2; }
+
+// the one upload behind both setters: `table` = [n_groups][stride] on the host (stride == 0: one row of n_per_group doubles)
+static int upload_target_params(lmc_engine* e, const double* table, int64_t n_groups, int64_t n_per_group, int64_t stride,
+                                int64_t first_chain, int64_t chains_per_group) {
+    const int64_t n = stride > 0 ? n_groups * stride : n_per_group;
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
     HIP_TRY(e, hipStreamSynchronize(main_stream(e)));
     dev_free(e, e->tparams);
     e->tparams = nullptr;
     int rc = dev_alloc(e, &e->tparams, static_cast<size_t>(n > 8 ? n : 8));
     if (rc != LMC_OK) return rc;
-    if (n > 0) HIP_TRY(e, hipMemcpyAsync(e->tparams, params, n * sizeof(double), hipMemcpyDefault, main_stream(e)));
-    e->n_tparams = n;
-    HIP_TRY(e, hipStreamSynchronize(main_stream(e)));
+    if (n > 0) HIP_TRY(e, hipMemcpyAsync(e->tparams, table, n * sizeof(double), hipMemcpyDefault, main_stream(e)));
+    e->n_tparams = n_per_group;
+    e->n_tgroups = n_groups;
+    e->A.tparam_stride = static_cast<int>(stride);
+    e->A.tparam_first = static_cast<int>(first_chain);
+    e->A.tparam_group = static_cast<int>(chains_per_group);
+    HIP_TRY(e, hipStreamSynchronize(main_stream(e)));   // (the copy has left `table` when this returns)
+    return LMC_OK;
+}
+
+int lmc_engine_set_target_params(lmc_engine* e, const double* params, int64_t n) {
+    if (!e || n < 0 || (n > 0 && !params)) return fail(e, LMC_ERR_INVALID, "bad target params");
+    const int rc = check_target_row(e, e->cfg.target_family, e->cfg.dim, n);
+    if (rc != LMC_OK) return rc;
+    return upload_target_params(e, params, 1, n, 0, 0, e->cfg.chains);   // one row, stride 0: every chain reads it
+}
+
+int lmc_engine_set_target_params_grouped(lmc_engine* e, const double* params, int64_t n_groups, int64_t n_per_group,
+                                         int64_t first_chain, int64_t chains_per_group) {
+    // (what needs no engine is looked at first: a host sees these refusals without a device, like lmc_engine_reserve_thinned's)
+    int rc = check_target_group_args(e, n_groups, n_per_group, first_chain, chains_per_group);
+    if (rc != LMC_OK) return rc;
+    if (!e) return fail(nullptr, LMC_ERR_INVALID, "null engine");
+    rc = check_target_groups(e, e->cfg.target_family, e->cfg.dim, e->cfg.chains, n_groups, n_per_group, first_chain, chains_per_group);
+    if (rc != LMC_OK) return rc;
+    if (n_per_group > 0 && !params) return fail(e, LMC_ERR_INVALID, "bad target params");
+    const int64_t stride = target_row_stride(n_per_group);
+    std::vector<double> table(static_cast<size_t>(n_groups * stride), 0.0);
+    for (int64_t g = 0; g < n_groups && n_per_group > 0; ++g)
+        std::memcpy(table.data() + g * stride, params + g * n_per_group, static_cast<size_t>(n_per_group) * sizeof(double));
+    return upload_target_params(e, table.data(), n_groups, n_per_group, stride, first_chain, chains_per_group);
+}
+
+int lmc_engine_target_groups(lmc_engine* e, int64_t* n_groups, int64_t* n_per_group, int64_t* first_chain, int64_t* chains_per_group) {
+    if (!e) return fail(nullptr, LMC_ERR_INVALID, "null engine");
+    if (n_groups) *n_groups = e->n_tgroups;
+    if (n_per_group) *n_per_group = e->n_tparams;
+    if (first_chain) *first_chain = e->A.tparam_first;
+    if (chains_per_group) *chains_per_group = e->A.tparam_group;
     return LMC_OK;
 }
 

@@ -99,6 +99,11 @@ struct ChainArrays {
     long long thin;        // every thin-th draw from trace_begin on is stored (lmc_engine_reserve_thinned; 1 = all of them)
     StatRecord* stat_rec; // [C][cap]: one 64-byte record of sampler statistics per draw
     long long cap;
+    // the target's parameter table (lmc_targets.hpp: target_param_row): chain c of this engine reads row
+    // (tparam_first + c) / tparam_group. (SamplerParams follows this struct in the kernarg segment: KernArgs below)
+    int tparam_stride;    // doubles between rows; 0 = one row for all chains
+    int tparam_first;     // job-wide index of this engine's chain 0
+    int tparam_group;     // chains per group, >= 1
 };
 
 struct SamplerParams {
@@ -1951,7 +1956,7 @@ __global__ __launch_bounds__(64 * W, run_waves_per_simd(NS, W)) void run_kernel(
     if (A0.status[c] & kStatusBadInitialEnergy) return;   // chain already aborted (ValueError on host)
 
     TargetT<NS> tgt;
-    tgt.init(tm, tparams, d);
+    tgt.init(tm, target_param_row(tparams, A0.tparam_stride, A0.tparam_first, A0.tparam_group, c), d);
 
     // ---- load persistent chain state
     double q[NS];

@@ -21,6 +21,16 @@
 
 namespace lmc {
 
+// Per-group parameters: `params` of a job is a table with one row per group of chains (ChainArrays::tparam_*,
+// lmc_engine_set_target_params_grouped). The row of the engine-wide chain index c -- blockIdx.x plus the launch's first
+// chain, never the bare block index -- is chosen ONCE, where the kernel calls init(); the functor sees its row as `params`
+// and nothing of the choice lives on into the iteration loop. stride == 0 is the job with one closure for every chain:
+// the pointer goes through as it came, without the division. Rows start 16-byte aligned (the stride is even).
+__device__ __forceinline__ const double* target_param_row(const double* tparams, int stride, int first, int group, int c) {
+    if (stride == 0) return tparams;
+    return tparams + static_cast<long long>(static_cast<unsigned>(first + c) / static_cast<unsigned>(group)) * stride;
+}
+
 enum TargetFamily : int {
     kStdNormal = 0,
     kDiagGaussian = 1,

@@ -15,7 +15,7 @@ __global__ __launch_bounds__(64) void logp_kernel(ChainArrays A, const double* t
     const int d = A.d;
     Team<1> tm{nullptr, 0};
     TargetT<NS> tgt;
-    tgt.init(tm, tparams, d);
+    tgt.init(tm, target_param_row(tparams, A.tparam_stride, A.tparam_first, A.tparam_group, c), d);
     double q[NS], g[NS];
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
@@ -43,7 +43,7 @@ __global__ __launch_bounds__(64) void trajectory_kernel(ChainArrays A, const dou
     const long long row = static_cast<long long>(c) * A.dpad;
     Team<1> tm{nullptr, 0};
     TargetT<NS> tgt;
-    tgt.init(tm, tparams, d);
+    tgt.init(tm, target_param_row(tparams, A.tparam_stride, A.tparam_first, A.tparam_group, c), d);
     double q[NS], p[NS], g[NS];
     float var[NS];
     double vard[NS];

@@ -410,7 +410,7 @@ __global__ __launch_bounds__(64 * W) void run_wide_kernel(ChainArrays A, DenseAr
     if (A.status[c] & kStatusBadInitialEnergy) return;
 
     TargetT<NS> tgt;
-    tgt.init(tm, tparams, d);
+    tgt.init(tm, target_param_row(tparams, A.tparam_stride, A.tparam_first, A.tparam_group, c), d);
     WideMass M;
     M.kind = D.covT == nullptr ? 0 : (D.mat_f64 ? 2 : 1);
     M.covT = D.covT == nullptr ? nullptr : static_cast<const char*>(D.covT) + static_cast<long long>(c) * D.mat_stride * (M.kind == 2 ? 8 : 4);
@@ -525,7 +525,7 @@ __global__ __launch_bounds__(64 * W) void wide_logp_kernel(ChainArrays A, const 
     tm.parity = 0;
     const int t = tm.tid();
     TargetT<NS> tgt;
-    tgt.init(tm, tparams, d);
+    tgt.init(tm, target_param_row(tparams, A.tparam_stride, A.tparam_first, A.tparam_group, c), d);
     double q[NS], g[NS];
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
@@ -558,7 +558,7 @@ __global__ __launch_bounds__(64 * W) void wide_trajectory_kernel(ChainArrays A, 
     tm.parity = 0;
     const int t = tm.tid();
     TargetT<NS> tgt;
-    tgt.init(tm, tparams, d);
+    tgt.init(tm, target_param_row(tparams, A.tparam_stride, A.tparam_first, A.tparam_group, c), d);
     WideMass M;
     M.kind = D.covT == nullptr ? 0 : (D.mat_f64 ? 2 : 1);
     M.covT = D.covT == nullptr ? nullptr : static_cast<const char*>(D.covT) + static_cast<long long>(c) * D.mat_stride * (M.kind == 2 ? 8 : 4);

@@ -56,6 +56,9 @@ def sample_distributed(logp_dlogp_func, model_ndim=None, draws=1000, tune=1000, 
 
     from .sampling import init_nuts, sample
 
+    if getattr(logp_dlogp_func, "groups", None) is not None:
+        raise NotImplementedError("sample_distributed does not take a targets.Batched yet: a rank's sample() call does not "
+                                  "know where its chain block lies in the job's groups")
     rank, world, local_rank = env_rank_world()
     if dist.is_available() and dist.is_initialized():
         rank, world = dist.get_rank(group), dist.get_world_size(group)

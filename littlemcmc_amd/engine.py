@@ -224,12 +224,41 @@ def hw_queue_cap(environ=None):
     return n if 1 <= n < 4 else None
 
 
+def _target_grouping(target, chains, first_chain, chains_per_group):
+    """(first_chain, chains_per_group) of an engine of ``chains`` chains on ``target``; (0, None) for every target that is
+    not a ``targets.Batched`` (one parameter row for all chains: the keywords are then refused unless left at their
+    defaults). Raises ValueError before anything is created."""
+    groups = getattr(target, "groups", None)
+    if groups is None:
+        if first_chain != 0 or chains_per_group is not None:
+            raise ValueError("first_chain / chains_per_group place an engine's chains in the groups of a targets.Batched; "
+                             "got %r" % (target,))
+        return 0, None
+    chains, first_chain = int(chains), int(first_chain)
+    if chains_per_group is None:
+        if chains % groups != 0:
+            raise ValueError("%d chains cannot be dealt evenly to the %d groups of %r (chains %% groups != 0); pass "
+                             "chains_per_group for an engine that holds part of a job" % (chains, groups, target))
+        chains_per_group = chains // groups
+    chains_per_group = int(chains_per_group)
+    if chains_per_group < 1 or first_chain < 0:
+        raise ValueError("chains_per_group must be >= 1 and first_chain >= 0 (got %d, %d)" % (chains_per_group, first_chain))
+    if target.row_of_chain(chains - 1, first_chain, chains_per_group) >= groups:
+        raise ValueError("chains [%d, %d) of the job in groups of %d chains reach past the %d groups of %r"
+                         % (first_chain, first_chain + chains, chains_per_group, groups, target))
+    return first_chain, chains_per_group
+
+
 class Engine:
     def __init__(self, target, chains, kind="nuts", potential="diag_adapt", device=0, lib_path=None,
                  target_accept=0.8, Emax=1000.0, adapt_step_size=True, step_scale=0.25, gamma=0.05, k=0.75,
                  t0=10, path_length=2.0, max_treedepth=10, early_max_treedepth=8, max_steps=1024,
                  adaptation_window=101, adaptation_window_multiplier=1.0, lds_levels=0, sdot=None, rng="numpy",
-                 mass_dtype="float32", lds_plan="auto", tuning=None):
+                 mass_dtype="float32", lds_plan="auto", tuning=None, first_chain=0, chains_per_group=None):
+        """``first_chain`` / ``chains_per_group``: for a ``targets.Batched`` target only -- this engine's chain c is chain
+        ``first_chain + c`` of the job and evaluates the density of group ``(first_chain + c) // chains_per_group``
+        (default: ``chains // groups``, the engine holds the whole job)."""
+        self.first_chain, self.chains_per_group = _target_grouping(target, chains, first_chain, chains_per_group)
         self._lib = _abi.load(lib_path or getattr(target, "lib_path", None))
         self._h = C.c_void_p()
         self.target = target
@@ -300,7 +329,11 @@ class Engine:
         self._check(self._lib.lmc_engine_create(C.byref(cfg), C.byref(h)), handle=None)
         self._h = h
         params = np.ascontiguousarray(target.params, dtype=np.float64)
-        self._check(self._lib.lmc_engine_set_target_params(self._h, _abi.ptr(params), params.size))
+        if self.chains_per_group is not None:   # targets.Batched: params is the [groups, n] table, one row per group of chains
+            self._check(self._lib.lmc_engine_set_target_params_grouped(self._h, _abi.ptr(params), params.shape[0], params.shape[1],
+                                                                       self.first_chain, self.chains_per_group))
+        else:
+            self._check(self._lib.lmc_engine_set_target_params(self._h, _abi.ptr(params), params.size))
         if hasattr(target, "_attach"):   # a run-time compiled density hands its kernels to the engine (targets.UserTarget)
             target._attach(self)
         self.capacity = 0
@@ -314,6 +347,13 @@ class Engine:
         a, b, c = C.c_int32(), C.c_int32(), C.c_int32()
         self._check(self._lib.lmc_engine_kernel_shape(self._h, C.byref(a), C.byref(b), C.byref(c)))
         return int(a.value), int(b.value), int(c.value)
+
+    def target_groups(self):
+        """(groups, parameters per group, first_chain, chains_per_group) as the engine holds them (lmc_engine_target_groups);
+        (1, n, 0, chains) for a target with one parameter vector for all chains."""
+        v = [C.c_int64() for _ in range(4)]
+        self._check(self._lib.lmc_engine_target_groups(self._h, *[C.byref(x) for x in v]))
+        return tuple(int(x.value) for x in v)
 
     # ---- plumbing ---------------------------------------------------------------------------------
     def _check(self, rc, handle=True):

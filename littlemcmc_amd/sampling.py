@@ -457,11 +457,18 @@ def _start_points(start, chains, model_ndim):
     return start
 
 
-def _make_engines(step, chains, devs):
+def _group_kw(first_chain, chains_per_group):
+    """Where an engine's chains lie in the groups of a ``targets.Batched`` job, as keywords of step._make_engine; nothing for
+    any other job (``chains_per_group`` None), whose engines are made with the arguments they always were."""
+    return {} if chains_per_group is None else {"first_chain": int(first_chain), "chains_per_group": int(chains_per_group)}
+
+
+def _make_engines(step, chains, devs, chains_per_group=None):
     """One Engine on one device; on several, an EngineGroup of one engine per contiguous chain block
-    (distributed.chain_block). If an engine cannot be made, the ones made before it are closed."""
+    (distributed.chain_block). If an engine cannot be made, the ones made before it are closed. ``chains_per_group`` (a
+    ``targets.Batched`` job): every engine learns its block's first chain, so a block may begin and end inside a group."""
     if len(devs) == 1:
-        return step._make_engine(chains, device=devs[0])
+        return step._make_engine(chains, device=devs[0], **_group_kw(0, chains_per_group))
     from .distributed import chain_block
     from .engine import EngineGroup
 
@@ -469,7 +476,7 @@ def _make_engines(step, chains, devs):
     made = []
     try:
         for dv, (b_lo, b_hi) in zip(devs, blocks):
-            made.append(step._make_engine(b_hi - b_lo, device=dv))
+            made.append(step._make_engine(b_hi - b_lo, device=dv, **_group_kw(b_lo, chains_per_group)))
     except BaseException:
         for e_ in made:
             e_.close()
@@ -591,6 +598,11 @@ def sample(logp_dlogp_func, model_ndim=None, draws=1000, tune=1000, step=None, i
     same job with ``thin=1``, in ``ceil((tune + draws - lo) / k)`` rows. The discarded draws are never stored, in HBM or
     over the host link (the sampling kernel skips their store), and the returned arrays are k times smaller. Only the
     outputs change: tuning, ``keep_moments``, the counters and warnings see every iteration.
+
+    A ``targets.Batched`` target runs many posteriors in one job: ``chains`` must be a multiple of its ``groups`` G, chain j
+    samples member ``j // (chains // G)`` and ``trace.reshape(G, chains // G, draws, ndim)`` is the per-posterior view --
+    each chain bit for bit the chain of that index of ``sample(batched[g], ...)`` with the same seeds and chain count,
+    whatever else is asked for (``thin``, ``stream_results``, ``devices``, ...). Not with a pooled mass matrix.
     """
     thin = _check_thin(thin)
     if model_ndim is None:
@@ -602,6 +614,10 @@ def sample(logp_dlogp_func, model_ndim=None, draws=1000, tune=1000, step=None, i
         cores = min(4, os.cpu_count() or 1)
     if chains is None:
         chains = max(2, cores)
+    def _per_group(tgt):   # many posteriors in one job (targets.Batched): contiguous blocks of chains // groups chains per group
+        return tgt.group_size(chains) if getattr(tgt, "groups", None) is not None else None
+
+    per_group = _per_group(target)
     seeds = _derive_seeds(random_seed, chains)
 
     if draws == 0:
@@ -616,6 +632,7 @@ def sample(logp_dlogp_func, model_ndim=None, draws=1000, tune=1000, step=None, i
         if start is None:
             start = start_
     starts = _start_points(start, chains, model_ndim)
+    per_group = _per_group(getattr(step, "_logp_dlogp_func", target))   # (the engines evaluate the STEP's density)
 
     tune, n_total = int(tune), int(tune) + int(draws)
     lo = tune if discard_tuned_samples else 0   # sampling.py:473-476
@@ -624,7 +641,7 @@ def sample(logp_dlogp_func, model_ndim=None, draws=1000, tune=1000, step=None, i
     def _probe_slots():   # resident wavefront slots of this job's sampling kernel on one GPU (a one-chain engine knows)
         if external:
             return chains + 1     # a host / torch callable is evaluated on one device: no automatic fan-out
-        probe = step._make_engine(1, device=0)
+        probe = step._make_engine(1, device=0, **_group_kw(0, per_group))
         try:
             return probe.resident_chains()
         finally:
@@ -632,6 +649,9 @@ def sample(logp_dlogp_func, model_ndim=None, draws=1000, tune=1000, step=None, i
 
     pooled = getattr(step.potential, "_pooled", False)
     if pooled:   # one matrix from the positions of all chains (QuadPotentialFullPooled): one GPU, enough chains, device iterations
+        if per_group is not None:
+            raise NotImplementedError("QuadPotentialFullPooled adapts ONE matrix from all chains; the chains of a Batched "
+                                      "target sample different posteriors (use adapt_full / adapt_diag: per chain)")
         step.potential.check_chains(chains)
         if external or getattr(step, "_host_step_rand", lambda: None)() is not None:
             raise NotImplementedError("a pooled dense mass matrix needs a device density and a device step_rand (the job "
@@ -641,7 +661,7 @@ def sample(logp_dlogp_func, model_ndim=None, draws=1000, tune=1000, step=None, i
     devs = _resolve_devices(devices, device, gpu_cap, chains, _probe_slots)
     if pooled and len(devs) > 1:
         raise NotImplementedError("a pooled dense mass matrix is adapted on one GPU (got devices=%r)" % (devs,))
-    eng = _make_engines(step, chains, devs)
+    eng = _make_engines(step, chains, devs, per_group)
     try:
         eng.seed(seeds)                       # np.random.seed(random_seed[i]) per chain (sampling.py:496-497)
         eng.set_position(np.ascontiguousarray(starts))

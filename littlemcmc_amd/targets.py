@@ -468,6 +468,101 @@ def _separable(cls, d, logp, grad, params=(), prelude=""):
 UserTarget.separable = classmethod(_separable)
 
 
+class Batched(DeviceTarget):
+    """Many posteriors in one job: ``Batched([member_0, ..., member_{G-1}])`` is the same device density with one parameter
+    vector per GROUP of chains -- the same model on G data sets, a temperature or prior-scale ladder, a sensitivity sweep.
+    ``sample(batched, chains=C)`` deals the chains to the groups in contiguous blocks of ``C // G`` (``C % G`` must be 0):
+    chain j samples ``members[j // (C // G)]``, so ``trace.reshape(G, C // G, draws, d)`` is the per-posterior view and every
+    chain is, bit for bit, the chain of the same index of ``sample(batched[g], chains=C)`` on the same seeds.
+
+    The members are device targets of ONE class with the same ``d`` and the same number of parameters (``UserTarget``
+    members: the same ``source`` and ``jit`` too -- the kernels are those of member 0, compiled once); ``TorchTarget``,
+    ``CallableTarget`` and nested ``Batched`` members are refused (a callable already sees all chains and can tell them
+    apart itself). ``params`` is the ``[G, n]`` table the engine uploads (lmc_engine_set_target_params_grouped: the kernels
+    pick a chain's row where they call the functor's ``init``), ``groups`` is G, ``members`` the list; ``batched[g]`` is member g
+    and ``len(batched)`` is G. A ``Batched`` cannot be called with one point -- a point has no group: call ``batched[g](q)``.
+
+    Diagnostics are per posterior: take R-hat / ESS over ``trace[sl]`` for ``sl`` in ``chain_slices(chains)``. R-hat ACROSS
+    groups is meaningless -- the groups' chains target different distributions and are supposed to disagree."""
+
+    def __init__(self, members):
+        members = list(members)
+        if not members:
+            raise ValueError("Batched needs at least one member target")
+        first = members[0]
+        for g, m in enumerate(members):
+            if not isinstance(m, DeviceTarget):
+                raise TypeError("Batched member %d is not a device target: %r" % (g, m))
+            if isinstance(m, (TorchTarget, Batched)):
+                raise TypeError("Batched member %d is a %s: a callable density already sees all chains (tell them apart in "
+                                "the callable), and a Batched cannot be nested" % (g, type(m).__name__))
+            if type(m) is not type(first):
+                raise TypeError("Batched member %d is a %s, member 0 a %s: the members share one class (one device functor)"
+                                % (g, type(m).__name__, type(first).__name__))
+            if m.d != first.d:
+                raise ValueError("Batched member %d has d = %d, member 0 has d = %d" % (g, m.d, first.d))
+            if m.params.shape != first.params.shape or m.params.ndim != 1:
+                raise ValueError("Batched member %d has %s parameters, member 0 has %s"
+                                 % (g, m.params.shape, first.params.shape))
+            if isinstance(m, UserTarget) and (m.source != first.source or m.jit != first.jit):
+                raise ValueError("Batched member %d has another source or jit than member 0: the members share one "
+                                 "compiled density and differ in their parameters only" % g)
+        super().__init__(first.d, np.stack([m.params for m in members]).reshape(len(members), first.params.size))
+        self.members = members
+        self.groups = len(members)
+        self.family = first.family
+        self.lib_path = first.lib_path
+
+    def __len__(self):
+        return self.groups
+
+    def __getitem__(self, g):
+        return self.members[g]
+
+    def __call__(self, q):
+        raise TypeError("a Batched target holds %d posteriors and one point has no group: call batched[g](q) for the "
+                        "density of group g" % self.groups)
+
+    def _wrap_logp(self, logp):
+        return self.members[0]._wrap_logp(logp)
+
+    # the kernels are member 0's: compiled (or fetched) once for all groups
+    def kernels_for(self, *args, **kwargs):
+        return self.members[0].kernels_for(*args, **kwargs)
+
+    def _attach(self, engine):
+        attach = getattr(self.members[0], "_attach", None)
+        if attach is not None:
+            attach(engine)
+
+    @staticmethod
+    def row_of_chain(chain, first_chain=0, chains_per_group=1):
+        """The group (row of ``params``) of chain ``chain`` of an engine whose chain 0 is chain ``first_chain`` of the job,
+        with ``chains_per_group`` chains per group: the host mirror of lmc_target_param_row."""
+        chain, first_chain, chains_per_group = int(chain), int(first_chain), int(chains_per_group)
+        if chain < 0 or first_chain < 0 or chains_per_group < 1:
+            raise ValueError("row_of_chain needs chain, first_chain >= 0 and chains_per_group >= 1 (got %r)"
+                             % ((chain, first_chain, chains_per_group),))
+        return (first_chain + chain) // chains_per_group
+
+    def group_size(self, chains):
+        """``chains // groups`` of a job of ``chains`` chains; ValueError unless the chains can be dealt evenly."""
+        chains = int(chains)
+        if chains < self.groups or chains % self.groups != 0:
+            raise ValueError("a Batched target of %d groups needs a multiple of %d chains (got chains=%d)"
+                             % (self.groups, self.groups, chains))
+        return chains // self.groups
+
+    def chain_slices(self, chains):
+        """One ``slice`` of the chain axis per group for a job of ``chains`` chains: ``trace[sl]`` are the chains of one
+        posterior -- what R-hat / ESS are taken over (across groups they are meaningless)."""
+        per = self.group_size(chains)
+        return [slice(g * per, (g + 1) * per) for g in range(self.groups)]
+
+    def __repr__(self):
+        return "Batched(%d x %s, d=%d)" % (self.groups, type(self.members[0]).__name__, self.d)
+
+
 def require_device_target(logp_dlogp_func, model_ndim=None):
     """What the step methods and ``sample()`` accept as ``logp_dlogp_func``: a device functor (inlined into the
     leapfrog kernel), a batched torch callable (TorchTarget) or -- the reference's own signature -- a plain per-point
@@ -478,7 +573,7 @@ def require_device_target(logp_dlogp_func, model_ndim=None):
             return CallableTarget(int(model_ndim), logp_dlogp_func)
         raise TypeError(
             "logp_dlogp_func must be a littlemcmc_amd.targets.DeviceTarget (StdNormal, DiagGaussian, AR1, Funnel, "
-            "Normal1D, UserTarget, TorchTarget) or a callable q[d] -> (logp, dlogp[d]) together with model_ndim; got %r"
+            "Normal1D, UserTarget, TorchTarget, Batched) or a callable q[d] -> (logp, dlogp[d]) together with model_ndim; got %r"
             % (logp_dlogp_func,))
     if model_ndim is not None and int(model_ndim) != logp_dlogp_func.d:
         raise ValueError("model_ndim=%s does not match the target's dimension %d" % (model_ndim, logp_dlogp_func.d))
