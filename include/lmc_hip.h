@@ -63,6 +63,34 @@ extern "C" {
 /* no device functor: the caller evaluates logp_dlogp_func for all chains between two lmc_engine_tick() calls
  * (a batched callable on device memory, e.g. torch-ROCm); all potentials (dense ones up to dim 256) */
 #define LMC_TARGET_EXTERNAL 6
+/* Generalised linear model that carries its data (additive within ABI 9; littlemcmc_amd/targets.py: GLM). Coefficients q[dim],
+ * design matrix X[N][dim], responses y[N], linear predictor eta = X q, prior q_e ~ N(0, 1/tau); constants that do not depend
+ * on q are dropped:
+ *   logp = sum_n l_n - 1/2 tau sum_e q_e^2,   g_e = sum_n X[n][e] r_n - tau q_e
+ *   LMC_GLM_BERNOULLI (logit link, y in {0, 1}):  l = y eta - softplus(eta),       r = y - sigmoid(eta)
+ *   LMC_GLM_POISSON   (log link, y >= 0):         l = y eta - exp(eta),            r = y - exp(eta)
+ *   LMC_GLM_GAUSSIAN  (identity, known sigma):    l = -1/2 (y - eta)^2 isig2,      r = (y - eta) isig2
+ * One chain is one wavefront: dim <= LMC_GLM_MAX_DIM, refused beyond. The parameter row is doubles only. With
+ * npad = N rounded up to a multiple of 64, d8 = dim rounded up to a multiple of 8 and dpad = 64 * (dim / 64 rounded up to a
+ * power of two: the lanes of the chain's wavefront times the elements each of them owns):
+ *   [0] likelihood code  [1] N  [2] npad  [3] tau = prior_scale^-2  [4] isig2 = sigma^-2  [5] dim  [6] dpad  [7] 0
+ *   [8, 8 + npad)                      y[n]
+ *   [8 + npad, +d8 * npad)             Xt[e][n] = X[n][e], row e at stride npad   (the eta pass: lane = observation)
+ *   [8 + npad * (1 + d8), +npad*dpad)  Xr[n][e] = X[n][e], row n at stride dpad   (the gradient pass: lane = coefficients)
+ * That is 8 + npad * (1 + d8 + dpad) doubles in all, below LMC_GLM_MAX_ROW (the device addresses a row with 32-bit byte
+ * offsets). Everything beyond n = N or e = dim is zero; every section starts 16-byte aligned (all offsets are even). The
+ * setters refuse (LMC_ERR_INVALID, before any HIP call) a row whose length is not the one its header and the engine's dim give,
+ * a header that does not match the engine's dim, and an unknown likelihood code; lmc_target_groups_check(), which sees no
+ * table, refuses a length that no N gives at that dim. X and y are finite (the padding rows of Xt are multiplied by the
+ * zero padding coefficients, not skipped). */
+/* (7 stays unassigned: lmc_has_target(7) is 0) */
+#define LMC_TARGET_GLM 8
+#define LMC_GLM_BERNOULLI 0
+#define LMC_GLM_POISSON 1
+#define LMC_GLM_GAUSSIAN 2
+#define LMC_GLM_MAX_DIM 512
+#define LMC_GLM_HEADER 8
+#define LMC_GLM_MAX_ROW (1LL << 29)
 
 /* Summation order of the float32 kinetic energy of the start state, 0.5f * sdot(p, v)
  * (integration.py:63-64 with float32 operands -> numpy -> OpenBLAS cblas_sdot). The value feeds the

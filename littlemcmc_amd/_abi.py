@@ -17,6 +17,9 @@ OK = 0
 KIND_NUTS, KIND_HMC = 0, 1
 POT_DIAG_ADAPT, POT_DIAG, POT_FULL, POT_FULL_INV, POT_FULL_ADAPT, POT_FULL_F64 = range(6)
 TARGET_STD_NORMAL, TARGET_DIAG_GAUSSIAN, TARGET_AR1, TARGET_FUNNEL, TARGET_NORMAL1D, TARGET_USER, TARGET_EXTERNAL = range(7)
+TARGET_GLM = 8   # (7 is unassigned) additive within ABI 9: a regression posterior that carries its data (include/lmc_hip.h: the row layout)
+GLM_BERNOULLI, GLM_POISSON, GLM_GAUSSIAN = 0, 1, 2
+GLM_MAX_DIM, GLM_HEADER, GLM_MAX_ROW = 512, 8, 1 << 29
 STATUS_BAD_INITIAL_ENERGY = 1
 SDOT_NATIVE, SDOT_OPENBLAS_SKYLAKEX, SDOT_OPENBLAS_HASWELL = 0, 1, 2
 RNG_NUMPY, RNG_PHILOX, RNG_COUNTER = 0, 1, 2

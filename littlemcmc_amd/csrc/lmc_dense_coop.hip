@@ -21,7 +21,7 @@ int dense_coop_lds_slots(int d, int dpad, int max_slots) {   // tree slots per c
 }
 
 typedef void (*CoopKernel)(ChainArrays, DenseArrays, SamplerParams, const double*, int);
-// the shared-matrix kernel of (family, ns), nullptr where there is none: the built-in families but the 1-D one (whatever the
+// the shared-matrix kernel of (family, ns), nullptr where there is none: the stock library's families but the 1-D one (whatever the
 // build), one or two elements per lane (dpad <= 128: the float32 matrix fits one CU's LDS next to the panels)
 template <template <int> class T>
 static CoopKernel coop_kernel_for(TargetTag<T>, int ns) {
@@ -31,7 +31,7 @@ static CoopKernel coop_kernel_for(TargetTag<T>, int ns) {
     });
 }
 static CoopKernel coop_kernel(int family, int ns) {
-    return with_builtin_target(family, [&](auto t) { return coop_kernel_for(t, ns); });
+    return with_stock_target(family, [&](auto t) { return coop_kernel_for(t, ns); });
 }
 
 int dense_coop_supported(int family, int ns, int d, int dpad) {

@@ -32,6 +32,18 @@ constexpr bool kUserCompiledIn = false;   // LMC_TARGET_USER runs kernels compil
 template <template <int> class T>
 struct TargetTag {};
 
+static_assert(kGlmHeader == LMC_GLM_HEADER && kGlmBernoulli == LMC_GLM_BERNOULLI && kGlmPoisson == LMC_GLM_POISSON &&
+              kGlmGaussian == LMC_GLM_GAUSSIAN && kGlmMaxDim == LMC_GLM_MAX_DIM && kGLM == LMC_TARGET_GLM, "lmc_targets.hpp and lmc_hip.h agree");
+
+// A family whose functor gathers across the lanes of ONE wavefront (GLMTarget) has kernels only where a chain is one
+// wavefront: a selector returns nullptr for it at any other shape (waves per chain > 1, more elements per lane than one wave
+// of the general kernels takes) instead of instantiating a kernel that could not run.
+template <template <int> class T>
+constexpr bool kOneWaveOnly = std::is_same<TargetTag<T>, TargetTag<GLMTarget>>::value;
+constexpr int kOneWaveMaxNs = 8;   // LMC_GLM_MAX_DIM / 64
+template <template <int> class T>
+constexpr bool has_shape(int ns, int w) { return !kOneWaveOnly<T> || (w == 1 && ns <= kOneWaveMaxNs); }
+
 // f(TargetTag<T>{}) for the functor of a built-in family, whatever LMC_ONLY_USER says; R{} (nullptr, false) for any other
 template <class F>
 auto with_builtin_target(int family, F&& f) {
@@ -46,6 +58,17 @@ auto with_builtin_target(int family, F&& f) {
     }
 }
 
+// ... and for the functor of any family of the stock library: the built-in ones and GLMTarget. GLMTarget is kept out of
+// with_builtin_target because that list is also what the test probe instantiates its kernels over, at EVERY shape (teams of 16
+// wavefronts, 16 elements per lane), and GLMTarget exists for one-wavefront chains only (has_shape).
+template <class F>
+auto with_stock_target(int family, F&& f) {
+#ifndef LMC_ONLY_USER   // (a private library around a user density stays without it)
+    if (family == LMC_TARGET_GLM) return f(TargetTag<GLMTarget>{});
+#endif
+    return with_builtin_target(family, f);
+}
+
 // f(TargetTag<T>{}) for every family whose kernels this build instantiates; R{} for a family it does not have. A JIT build
 // around a user density (LMC_USER_TARGET_HEADER with LMC_ONLY_USER) has that family only: seconds to compile, not a minute.
 template <class F>
@@ -55,10 +78,10 @@ auto with_target(int family, F&& f) {
 #ifdef LMC_ONLY_USER
     return decltype(f(TargetTag<UserTarget>{})){};
 #else
-    return with_builtin_target(family, f);
+    return with_stock_target(family, f);
 #endif
 #else
-    return with_builtin_target(family, f);
+    return with_stock_target(family, f);
 #endif
 }
 

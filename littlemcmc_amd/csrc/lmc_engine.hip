@@ -746,14 +746,18 @@ typedef void (*RunKernel)(ChainArrays, SamplerParams, const double*);
 // of the kernel chosen here (same plan, same leaf group).
 template <int NS, int W, template <int> class T>
 static RunKernel run_kernel_of_shape(const lmc_engine* e, int plan) {
-    if (e->cfg.rng_mode == LMC_RNG_PHILOX) return &run_kernel<NS, W, T, 1>;
-    if (e->cfg.rng_mode == LMC_RNG_COUNTER) return &run_kernel<NS, W, T, 2>;
-    if constexpr (W == 1) {
-        const bool pinned_pairs = e->leaf_group != run_leaf_group(NS, 1);
-        if (plan == 1) return pinned_pairs ? &run_kernel<NS, 1, T, 0, 1, 2> : &run_kernel<NS, 1, T, 0, 1>;
-        if (pinned_pairs) return &run_kernel<NS, 1, T, 0, 0, 2>;
+    if constexpr (!has_shape<T>(NS, W)) {
+        return nullptr;
+    } else {
+        if (e->cfg.rng_mode == LMC_RNG_PHILOX) return &run_kernel<NS, W, T, 1>;
+        if (e->cfg.rng_mode == LMC_RNG_COUNTER) return &run_kernel<NS, W, T, 2>;
+        if constexpr (W == 1) {
+            const bool pinned_pairs = e->leaf_group != run_leaf_group(NS, 1);
+            if (plan == 1) return pinned_pairs ? &run_kernel<NS, 1, T, 0, 1, 2> : &run_kernel<NS, 1, T, 0, 1>;
+            if (pinned_pairs) return &run_kernel<NS, 1, T, 0, 0, 2>;
+        }
+        return &run_kernel<NS, W, T>;
     }
-    return &run_kernel<NS, W, T>;
 }
 template <template <int> class T>
 static RunKernel run_kernel_for(TargetTag<T>, const lmc_engine* e, int plan) {
@@ -770,11 +774,17 @@ static RunKernel sampling_kernel(const lmc_engine* e, int plan) {
 // the unit kernels over the target family (lmc_unit_kernels.hpp)
 template <template <int> class T>
 static auto trajectory_kernel_for(TargetTag<T>, int ns) {
-    return with_int<1, 2, 4, 8, 16>(ns, [](auto NS) { return &trajectory_kernel<NS, T>; });
+    return with_int<1, 2, 4, 8, 16>(ns, [](auto NS) -> decltype(&trajectory_kernel<1, T>) {
+        if constexpr (has_shape<T>(NS, 1)) return &trajectory_kernel<NS, T>;
+        else return nullptr;
+    });
 }
 template <template <int> class T>
 static auto logp_kernel_for(TargetTag<T>, int ns) {
-    return with_int<1, 2, 4, 8, 16>(ns, [](auto NS) { return &logp_kernel<NS, T>; });
+    return with_int<1, 2, 4, 8, 16>(ns, [](auto NS) -> decltype(&logp_kernel<1, T>) {
+        if constexpr (has_shape<T>(NS, 1)) return &logp_kernel<NS, T>;
+        else return nullptr;
+    });
 }
 
 static int ns_for_dim(int d) {
@@ -879,7 +889,12 @@ int lmc_engine_create(const lmc_config* cfg, lmc_engine** out) {
     // that the goldens of the small shapes replay through them too
     const bool forced = cfg->tuning.force_general != 0 && cfg->rng_mode == LMC_RNG_NUMPY &&
                         (cfg->target_family != LMC_TARGET_EXTERNAL || cfg->potential < LMC_POT_FULL);
-    const bool wide = cfg->dim > 1024 || (cfg->potential >= LMC_POT_FULL && cfg->dim > 256) || cfg->mass_f64 != 0 || rtc_dense || forced;
+    // (a GLM chain is one wavefront: beyond the fused one-wave shapes, 256 dimensions, it runs in the one-wave general kernels)
+    if (cfg->target_family == LMC_TARGET_GLM && cfg->dim > LMC_GLM_MAX_DIM)
+        return fail(nullptr, LMC_ERR_INVALID, "LMC_TARGET_GLM supports dim <= %d, one wavefront per chain (got %d)", LMC_GLM_MAX_DIM, cfg->dim);
+    const bool glm_general = cfg->target_family == LMC_TARGET_GLM && cfg->dim > 256;
+    const bool wide = cfg->dim > 1024 || (cfg->potential >= LMC_POT_FULL && cfg->dim > 256) || cfg->mass_f64 != 0 || rtc_dense || forced ||
+                      glm_general;
     if (wide) {
         if (cfg->dim > kWideMaxDim)
             return fail(nullptr, LMC_ERR_INVALID, "dim %d is beyond the general kernels' %d", cfg->dim, kWideMaxDim);
@@ -1465,14 +1480,55 @@ int lmc_target_param_row(int64_t chain, int64_t first_chain, int64_t chains_per_
     return LMC_OK;
 }
 
+// doubles of a GLM row of n_obs observations at dimension dim (include/lmc_hip.h: LMC_TARGET_GLM)
+static int64_t glm_npad(int64_t n_obs) { return (n_obs + 63) / 64 * 64; }
+static int64_t glm_row_doubles(int64_t n_obs, int dim) {
+    return LMC_GLM_HEADER + glm_npad(n_obs) * (1 + static_cast<int64_t>(dim + 7) / 8 * 8 + 64 * ns_for_dim(dim));
+}
+
 // the length a family's functor reads (lmc_targets.hpp), checked per row
 static int check_target_row(lmc_engine* e, int family, int dim, int64_t n) {
+    if (family == LMC_TARGET_GLM) {   // (the header is looked at where there is a table: check_glm_rows)
+        if (dim > LMC_GLM_MAX_DIM) return fail(e, LMC_ERR_INVALID, "glm supports dim <= %d (got %d)", LMC_GLM_MAX_DIM, dim);
+        const int64_t per64 = glm_row_doubles(64, dim) - LMC_GLM_HEADER;
+        if (n <= LMC_GLM_HEADER || (n - LMC_GLM_HEADER) % per64 != 0)
+            return fail(e, LMC_ERR_INVALID, "glm: no number of observations gives a row of %lld doubles at dim %d "
+                                            "(8 + npad * (1 + d8 + dpad), npad a multiple of 64)", (long long)n, dim);
+        if (n >= LMC_GLM_MAX_ROW)
+            return fail(e, LMC_ERR_INVALID, "glm: a row of %lld doubles is beyond the %lld the device addresses with 32-bit byte offsets",
+                        (long long)n, (long long)LMC_GLM_MAX_ROW);
+    }
     if (family == LMC_TARGET_DIAG_GAUSSIAN && n != dim)
         return fail(e, LMC_ERR_INVALID, "diag_gaussian needs %d precisions, got %lld", dim, (long long)n);
     if (family == LMC_TARGET_AR1 && n != 3)
         return fail(e, LMC_ERR_INVALID, "ar1 needs params {c_end, c_mid, off}");
     if (family == LMC_TARGET_NORMAL1D && n != 2)
         return fail(e, LMC_ERR_INVALID, "normal1d needs params {loc, scale}");
+    return LMC_OK;
+}
+
+// A GLM table's rows against their own headers, before any HIP call: likelihood code, N and its padding, the engine's dim and
+// lane layout, and the length all of these give.
+static int check_glm_rows(lmc_engine* e, int family, int dim, const double* table, int64_t n_groups, int64_t n_per_group) {
+    if (family != LMC_TARGET_GLM) return LMC_OK;
+    if (!table || n_per_group < LMC_GLM_HEADER) return fail(e, LMC_ERR_INVALID, "glm: a row begins with a header of %d doubles", LMC_GLM_HEADER);
+    for (int64_t g = 0; g < n_groups; ++g) {
+        const double* h = table + g * n_per_group;
+        if (!(h[0] == LMC_GLM_BERNOULLI || h[0] == LMC_GLM_POISSON || h[0] == LMC_GLM_GAUSSIAN))
+            return fail(e, LMC_ERR_INVALID, "glm row %lld: unknown likelihood code %g", (long long)g, h[0]);
+        if (!(h[1] >= 1.0 && h[1] < 2147483648.0) || h[1] != std::floor(h[1]))
+            return fail(e, LMC_ERR_INVALID, "glm row %lld: N = %g is not a count of observations", (long long)g, h[1]);
+        const int64_t n_obs = static_cast<int64_t>(h[1]);
+        if (h[2] != static_cast<double>(glm_npad(n_obs)) || h[5] != static_cast<double>(dim) || h[6] != 64.0 * ns_for_dim(dim))
+            return fail(e, LMC_ERR_INVALID, "glm row %lld: header {npad %g, dim %g, dpad %g} does not match N = %lld at the engine's dim %d "
+                                            "(npad %lld, dpad %d)", (long long)g, h[2], h[5], h[6], (long long)n_obs, dim,
+                        (long long)glm_npad(n_obs), 64 * ns_for_dim(dim));
+        if (n_per_group != glm_row_doubles(n_obs, dim))
+            return fail(e, LMC_ERR_INVALID, "glm row %lld: %lld doubles, but N = %lld at dim %d takes %lld", (long long)g,
+                        (long long)n_per_group, (long long)n_obs, dim, (long long)glm_row_doubles(n_obs, dim));
+        if (!(h[3] > 0.0) || !(h[4] > 0.0) || !std::isfinite(h[3]) || !std::isfinite(h[4]))
+            return fail(e, LMC_ERR_INVALID, "glm row %lld: tau and isig2 must be positive and finite", (long long)g);
+    }
     return LMC_OK;
 }
 
@@ -1532,7 +1588,9 @@ static int upload_target_params(lmc_engine* e, const double* table, int64_t n_gr
 
 int lmc_engine_set_target_params(lmc_engine* e, const double* params, int64_t n) {
     if (!e || n < 0 || (n > 0 && !params)) return fail(e, LMC_ERR_INVALID, "bad target params");
-    const int rc = check_target_row(e, e->cfg.target_family, e->cfg.dim, n);
+    int rc = check_target_row(e, e->cfg.target_family, e->cfg.dim, n);
+    if (rc != LMC_OK) return rc;
+    rc = check_glm_rows(e, e->cfg.target_family, e->cfg.dim, params, 1, n);
     if (rc != LMC_OK) return rc;
     return upload_target_params(e, params, 1, n, 0, 0, e->cfg.chains);   // one row, stride 0: every chain reads it
 }
@@ -1546,6 +1604,8 @@ int lmc_engine_set_target_params_grouped(lmc_engine* e, const double* params, in
     rc = check_target_groups(e, e->cfg.target_family, e->cfg.dim, e->cfg.chains, n_groups, n_per_group, first_chain, chains_per_group);
     if (rc != LMC_OK) return rc;
     if (n_per_group > 0 && !params) return fail(e, LMC_ERR_INVALID, "bad target params");
+    rc = check_glm_rows(e, e->cfg.target_family, e->cfg.dim, params, n_groups, n_per_group);
+    if (rc != LMC_OK) return rc;
     const int64_t stride = target_row_stride(n_per_group);
     std::vector<double> table(static_cast<size_t>(n_groups * stride), 0.0);
     for (int64_t g = 0; g < n_groups && n_per_group > 0; ++g)

@@ -2089,14 +2089,27 @@ __global__ __launch_bounds__(64 * W, run_waves_per_simd(NS, W)) void run_kernel(
         TransitionOut out;
         if (P.kind == 0) {
             const int md = (tune && iter_count < 200) ? P.early_max_treedepth : P.max_treedepth;
+            // (a density whose body is beyond the inliner's budget -- lmc_targets.hpp: kInlineTransition -- has the transition
+            // inlined all the same: as a call it would take q, p0, g0 through scratch memory. Every other density takes the
+            // plain statement, as before.)
+            if constexpr (InlineTransition<TargetT<NS>>::value) {
+                [[clang::always_inline]] nuts_transition2<NS, LP, G>(tm, tgt, vard, rng, cx, qrow, q, p0, g0, e0, logp0, step_size,
+                                                                     P.emax, md, momentum_f32, out);
+            } else {
             nuts_transition2<NS, LP, G>(tm, tgt, vard, rng, cx, qrow, q, p0, g0, e0, logp0, step_size, P.emax, md,
                                  momentum_f32, out);
+            }
             vload<NS>(qrow, q);   // the proposal was written to the chain's row of A.q
             // (handing it over in registers when the last doubling accepted it measured -4 % on depth-3 trees)
             if (out.exhausted && !tune) ++ct_maxdepth;
         } else {
+            if constexpr (InlineTransition<TargetT<NS>>::value) {
+                [[clang::always_inline]] hmc_transition<NS>(tm, tgt, vard, rng, q, p0, g0, e0, logp0, step_size, P.emax,
+                                                            P.path_length, P.max_steps, out);
+            } else {
             hmc_transition<NS>(tm, tgt, vard, rng, q, p0, g0, e0, logp0, step_size, P.emax, P.path_length,
                                P.max_steps, out);
+            }
         }
         ct_leap += out.n_leapfrog;
         LMC_PHASE(2)

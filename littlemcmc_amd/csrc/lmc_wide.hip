@@ -25,15 +25,24 @@ static auto with_wide_shape(int ns, int w, F&& f) {
 }
 template <template <int> class T>
 static auto run_wide_for(TargetTag<T>, int ns, int w) {
-    return with_wide_shape(ns, w, [](auto NS, auto W) { return &run_wide_kernel<NS, W, T>; });
+    return with_wide_shape(ns, w, [](auto NS, auto W) -> decltype(&run_wide_kernel<1, 1, T>) {
+        if constexpr (has_shape<T>(NS, W)) return &run_wide_kernel<NS, W, T>;
+        else return nullptr;
+    });
 }
 template <template <int> class T>
 static auto logp_wide_for(TargetTag<T>, int ns, int w) {
-    return with_wide_shape(ns, w, [](auto NS, auto W) { return &wide_logp_kernel<NS, W, T>; });
+    return with_wide_shape(ns, w, [](auto NS, auto W) -> decltype(&wide_logp_kernel<1, 1, T>) {
+        if constexpr (has_shape<T>(NS, W)) return &wide_logp_kernel<NS, W, T>;
+        else return nullptr;
+    });
 }
 template <template <int> class T>
 static auto trajectory_wide_for(TargetTag<T>, int ns, int w) {
-    return with_wide_shape(ns, w, [](auto NS, auto W) { return &wide_trajectory_kernel<NS, W, T>; });
+    return with_wide_shape(ns, w, [](auto NS, auto W) -> decltype(&wide_trajectory_kernel<1, 1, T>) {
+        if constexpr (has_shape<T>(NS, W)) return &wide_trajectory_kernel<NS, W, T>;
+        else return nullptr;
+    });
 }
 
 int wide_scratch_slots(int max_levels) { return wide_scratch_vectors(max_levels); }

@@ -7,6 +7,8 @@ The objects here name such a functor plus its parameters; they are ALSO callable
 reference's signature -- the call evaluates the device functor on the GPU for one point -- so
 they can be passed wherever the reference expects ``logp_dlogp_func``.
 
+:class:`GLM` is the built-in family that carries data: a bernoulli / poisson / gaussian regression on ``X`` and ``y``.
+
 Arbitrary densities are supported three ways: :class:`UserTarget` compiles a user-supplied HIP snippet into the
 kernels (the fast path), :class:`TorchTarget` takes a batched torch callable on the GPU, and a plain per-point
 Python callable -- the reference's own plug-in signature -- is wrapped in :class:`CallableTarget`: the sampler still
@@ -103,6 +105,112 @@ class Normal1D(DeviceTarget):
 
     def _wrap_logp(self, logp):
         return np.array([logp])
+
+
+def glm_ns(d):
+    """Elements per lane of a one-wavefront chain of dimension ``d``: ceil(d / 64) rounded up to a power of two."""
+    need, ns = (int(d) + 63) // 64, 1
+    while ns < need:
+        ns *= 2
+    return ns
+
+
+def glm_row_layout(n_obs, d):
+    """Offsets (in doubles) of the sections of a GLM parameter row (include/lmc_hip.h: LMC_TARGET_GLM):
+    ``dict(npad, d8, dpad, y, xt, xr, size)``. They depend on (N, d) only, and all of them are even."""
+    n_obs, d = int(n_obs), int(d)
+    npad = (n_obs + 63) // 64 * 64
+    d8 = (d + 7) // 8 * 8
+    dpad = 64 * glm_ns(d)
+    y0 = _abi.GLM_HEADER
+    xt0 = y0 + npad
+    xr0 = xt0 + d8 * npad
+    return dict(npad=npad, d8=d8, dpad=dpad, y=y0, xt=xt0, xr=xr0, size=xr0 + npad * dpad)
+
+
+def glm_row(X, y, code, tau, isig2):
+    """The parameter row of a GLM: header {likelihood code, N, npad, tau, isig2, d, dpad, 0}, y[npad], Xt[d8][npad] (the eta
+    pass reads an observation per lane, eight rows at a time), Xr[npad][dpad] (the gradient pass reads a lane's coefficients
+    of one observation); everything beyond n = N or e = d is zero."""
+    n_obs, d = X.shape
+    lay = glm_row_layout(n_obs, d)
+    if lay["size"] >= _abi.GLM_MAX_ROW:
+        raise ValueError("GLM: N = %d observations at d = %d make a parameter row of %d doubles; the device addresses a row "
+                         "with 32-bit byte offsets (below %d doubles)" % (n_obs, d, lay["size"], _abi.GLM_MAX_ROW))
+    row = np.zeros(lay["size"], dtype=np.float64)
+    row[:7] = [code, n_obs, lay["npad"], tau, isig2, d, lay["dpad"]]
+    row[lay["y"]:lay["y"] + n_obs] = y
+    row[lay["xt"]:lay["xr"]].reshape(lay["d8"], lay["npad"])[:d, :n_obs] = X.T
+    row[lay["xr"]:].reshape(lay["npad"], lay["dpad"])[:n_obs, :d] = X
+    return row
+
+
+class GLM(DeviceTarget):
+    """A regression posterior that carries its data: ``GLM(X, y, likelihood="bernoulli" | "poisson" | "gaussian",
+    prior_scale=1.0, sigma=1.0)`` with ``X`` float64 ``[N, d]``, ``y`` float64 ``[N]`` and coefficients ``q`` of length
+    ``d = X.shape[1]``. The linear predictor is ``eta = X q`` (an intercept is a column of ones in ``X``; there is no offset),
+    the prior ``q_e ~ N(0, prior_scale**2)``:
+
+        logp = sum_n l_n - tau/2 sum_e q_e^2,    g_e = sum_n X[n, e] r_n - tau q_e,    tau = prior_scale**-2
+
+        bernoulli (logit link, y in {0, 1}):  l = y eta - softplus(eta),           r = y - sigmoid(eta)
+        poisson   (log link, y >= 0):         l = y eta - exp(eta),                r = y - exp(eta)
+        gaussian  (identity, known sigma):    l = -(y - eta)^2 / (2 sigma^2),      r = (y - eta) / sigma^2
+
+    Additive constants that do not depend on ``q`` are DROPPED (log y!, log(sigma sqrt(2 pi)), the prior's normaliser): the
+    value is the log posterior up to a constant, which is all a sampler needs; it is not a normalised log-likelihood.
+    softplus and sigmoid are evaluated in their stable forms (finite for |eta| up to 800 and beyond); an overflowing exp(eta)
+    of the poisson likelihood gives a non-finite logp, which the sampler reports as a divergence.
+
+    One chain is one wavefront, so ``d <= 512``. The target is a plain device target -- NUTS / HMC, ``thin=``,
+    ``rng="counter"``, dense mass matrices, ``devices=`` -- and a member of :class:`Batched`: the same model on many data
+    sets is ``Batched([GLM(X_g, y_g, ...) for g in ...])`` with equal ``N``, ``d`` and likelihood."""
+
+    family = _abi.TARGET_GLM
+    LIKELIHOODS = {"bernoulli": _abi.GLM_BERNOULLI, "poisson": _abi.GLM_POISSON, "gaussian": _abi.GLM_GAUSSIAN}
+
+    def __init__(self, X, y, likelihood="bernoulli", prior_scale=1.0, sigma=1.0):
+        X = np.array(X, dtype=np.float64, order="C")
+        y = np.array(y, dtype=np.float64, order="C")
+        if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1:
+            raise ValueError("GLM: X must be [N, d] with N, d >= 1 (got shape %s)" % (X.shape,))
+        if y.shape != (X.shape[0],):
+            raise ValueError("GLM: y must be [N] = [%d] (got shape %s)" % (X.shape[0], y.shape))
+        if X.shape[1] > _abi.GLM_MAX_DIM:
+            raise ValueError("GLM: d = %d is beyond %d (one wavefront per chain); use a TorchTarget for wider models"
+                             % (X.shape[1], _abi.GLM_MAX_DIM))
+        if likelihood not in self.LIKELIHOODS:
+            raise ValueError("GLM: likelihood must be one of %s (got %r)" % (sorted(self.LIKELIHOODS), likelihood))
+        if not (np.isfinite(X).all() and np.isfinite(y).all()):
+            raise ValueError("GLM: X and y must be finite")
+        if likelihood == "bernoulli" and not np.isin(y, (0.0, 1.0)).all():
+            raise ValueError("GLM: bernoulli y must be 0 or 1")
+        if likelihood == "poisson" and (y < 0).any():
+            raise ValueError("GLM: poisson y must be >= 0")
+        prior_scale, sigma = float(prior_scale), float(sigma)
+        if not (np.isfinite(prior_scale) and prior_scale > 0.0 and np.isfinite(sigma) and sigma > 0.0):
+            raise ValueError("GLM: prior_scale and sigma must be positive and finite (got %r, %r)" % (prior_scale, sigma))
+        self.X, self.y = X, y
+        self.likelihood = likelihood
+        self.n_obs = X.shape[0]
+        self.prior_scale, self.sigma = prior_scale, sigma
+        self.tau, self.isig2 = prior_scale ** -2, sigma ** -2
+        if not (np.isfinite(self.tau) and self.tau > 0.0 and np.isfinite(self.isig2) and self.isig2 > 0.0):
+            raise ValueError("GLM: prior_scale**-2 and sigma**-2 must be positive and finite")
+        super().__init__(X.shape[1], glm_row(X, y, self.LIKELIHOODS[likelihood], self.tau, self.isig2))
+
+    def posterior_gaussian(self):
+        """``(mean[d], cov[d, d])`` of the exact posterior of the gaussian likelihood (host numpy):
+        ``cov = (X'X / sigma^2 + tau I)^-1``, ``mean = cov X'y / sigma^2``."""
+        if self.likelihood != "gaussian":
+            raise ValueError("posterior_gaussian() is the closed form of likelihood='gaussian' (this is %r)" % self.likelihood)
+        prec = self.X.T @ self.X * self.isig2 + self.tau * np.eye(self.d)
+        cov = np.linalg.inv(prec)
+        cov = 0.5 * (cov + cov.T)
+        return np.linalg.solve(prec, self.X.T @ self.y * self.isig2), cov
+
+    def __repr__(self):
+        return "GLM(%s, N=%d, d=%d)" % (self.likelihood, self.n_obs, self.d)
 
 
 class UserTarget(DeviceTarget):
@@ -504,6 +612,10 @@ class Batched(DeviceTarget):
             if m.params.shape != first.params.shape or m.params.ndim != 1:
                 raise ValueError("Batched member %d has %s parameters, member 0 has %s"
                                  % (g, m.params.shape, first.params.shape))
+            if isinstance(m, GLM) and (m.likelihood != first.likelihood or m.n_obs != first.n_obs):
+                raise ValueError("Batched member %d is a %s GLM of N = %d, member 0 a %s GLM of N = %d: the members share one "
+                                 "likelihood and one number of observations (rows of equal length can still differ in both)"
+                                 % (g, m.likelihood, m.n_obs, first.likelihood, first.n_obs))
             if isinstance(m, UserTarget) and (m.source != first.source or m.jit != first.jit):
                 raise ValueError("Batched member %d has another source or jit than member 0: the members share one "
                                  "compiled density and differ in their parameters only" % g)
@@ -573,7 +685,7 @@ def require_device_target(logp_dlogp_func, model_ndim=None):
             return CallableTarget(int(model_ndim), logp_dlogp_func)
         raise TypeError(
             "logp_dlogp_func must be a littlemcmc_amd.targets.DeviceTarget (StdNormal, DiagGaussian, AR1, Funnel, "
-            "Normal1D, UserTarget, TorchTarget, Batched) or a callable q[d] -> (logp, dlogp[d]) together with model_ndim; got %r"
+            "Normal1D, GLM, UserTarget, TorchTarget, Batched) or a callable q[d] -> (logp, dlogp[d]) together with model_ndim; got %r"
             % (logp_dlogp_func,))
     if model_ndim is not None and int(model_ndim) != logp_dlogp_func.d:
         raise ValueError("model_ndim=%s does not match the target's dimension %d" % (model_ndim, logp_dlogp_func.d))

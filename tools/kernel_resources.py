@@ -6,7 +6,7 @@ import sys
 
 args = sys.argv[1:]
 unit = "lmc_engine"
-if args and args[0] in ("lmc_engine", "lmc_dense"):   # translation unit to analyse (default: the diagonal kernels)
+if args and args[0] in ("lmc_engine", "lmc_dense", "lmc_dense_coop", "lmc_wide"):   # translation unit to analyse (default: the diagonal kernels)
     unit = args.pop(0)
 cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-c", "-mllvm", "-disable-machine-licm",
        "-I", "littlemcmc_amd/csrc", "-Rpass-analysis=kernel-resource-usage", "-o", "/tmp/lmc_kres.o",
@@ -27,6 +27,6 @@ for line in out.splitlines():
 for r in rows:
     name = subprocess.run(["c++filt", r["name"]], capture_output=True, text=True).stdout.strip()
     name = re.sub(r"\(.*", "", name).replace("void lmc::", "").replace("lmc::", "")
-    print("%-46s sgpr %3d vgpr %3d agpr %3d scratch %5d occ %d" % (
-        name[:46], r.get("TotalSGPRs", -1), r.get("VGPRs", -1), r.get("AGPRs", -1),
+    print("%-52s sgpr %3d vgpr %3d agpr %3d scratch %5d occ %d" % (
+        name[:52], r.get("TotalSGPRs", -1), r.get("VGPRs", -1), r.get("AGPRs", -1),
         r.get("ScratchSize [bytes/lane]", -1), r.get("Occupancy [waves/SIMD]", -1)))
