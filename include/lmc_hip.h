@@ -655,10 +655,23 @@ int lmc_engine_load_user_run_plan1(lmc_engine* e, const char* run_name_plan1);
  *   out[3 + k][dim] = sum of biased (1/n) autocovariances at lag lag0 + k, k < lmc_diag_lags_per_pass()
  * out is a DEVICE pointer to (3 + lags_per_pass) * dim doubles. The work is enqueued on `stream` (a hipStream_t, NULL =
  * default stream) of the current device; the result is bit-reproducible (no floating-point atomics). The statistics add
- * over chains, chain halves and ranks: split R-hat and the Geyer ESS follow from their sums (littlemcmc_amd/diagnostics.py). */
+ * over chains, chain halves and ranks: split R-hat and the Geyer ESS follow from their sums (littlemcmc_amd/diagnostics.py).
+ * Refused with LMC_ERR_INVALID before any HIP call: NULL x or out, chains outside [1, 2^31) (chain indices are 32-bit in the
+ * group arithmetic this call shares with the grouped one below), dim < 1, n < 2, t0 < 0, t0 + n > draws_stride, lag0 < 0. */
 int lmc_diag_lags_per_pass(void);
 int lmc_diag_chain_stats(const double* x, int64_t chains, int64_t draws_stride, int32_t dim, int64_t t0, int64_t n,
                          int32_t lag0, double* out, void* stream);
+/* Additive within ABI 9: the same statistics PER GROUP of chains (many posteriors in one job, targets.Batched) in one pass.
+ * x is a trace block whose chain 0 is chain first_chain of the job; chain c of the block belongs to group
+ * (first_chain + c) / chains_per_group (lmc_target_param_row). The block touches the groups g0 = first_chain / chains_per_group
+ * .. g1 = (first_chain + chains - 1) / chains_per_group, and out is [g1 - g0 + 1][3 + lags_per_pass][dim] doubles (DEVICE):
+ * the block above once per touched group, in group order. A first or last group that lies only partly inside the block
+ * gets the sums over its chains that are present -- the statistics add over chains, so the parts of a group that straddles
+ * two blocks (two GPUs) are simply added. Bit-reproducible like the ungrouped call, which IS this call with first_chain 0
+ * and chains_per_group = chains. Refused with LMC_ERR_INVALID before any HIP call: what lmc_diag_chain_stats refuses,
+ * first_chain < 0, chains_per_group < 1, first_chain + chains outside [1, 2^31). */
+int lmc_diag_chain_stats_grouped(const double* x, int64_t chains, int64_t draws_stride, int32_t dim, int64_t t0, int64_t n,
+                                 int32_t lag0, int64_t first_chain, int64_t chains_per_group, double* out, void* stream);
 
 #ifdef __cplusplus
 }

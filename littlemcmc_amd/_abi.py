@@ -197,6 +197,8 @@ _SIGNATURES = {
     "lmc_engine_load_user_run_plan1": (C.c_int, [_P, C.c_char_p]),
     "lmc_diag_lags_per_pass": (C.c_int, []),
     "lmc_diag_chain_stats": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int32, _P, _P]),
+    "lmc_diag_chain_stats_grouped": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int64,
+                                               C.c_int64, _P, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -14,6 +14,12 @@
 // Blocks loop over chains and keep running sums; a second kernel adds the per-block partials in a fixed order, so the
 // result is bit-reproducible (no floating-point atomics). Bound: HBM (the trace is read twice per pass; 16 loads of
 // 512 B in flight per wave); algorithmic bytes = 2 x 8 x chains x n x dim per pass.
+//
+// Groups (targets.Batched: many posteriors in one job): chain j of the JOB is in group j / chains_per_group
+// (lmc_target_param_row), and the statistics are wanted per group. The block index is (group, chain block, slab); a block
+// loops over ITS group's chains inside the trace block, and the reduction adds a group's chain blocks. The ~4096
+// wavefronts of a launch are shared by the groups, so many small groups get one block each and the partial buffer stays
+// at the size of the result. The ungrouped call is the one-group call of the same code.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -26,10 +32,18 @@ constexpr int kDiagRows = 3 + kDiagLags;      // sum mean, sum mean^2, sum var, 
 
 __global__ __launch_bounds__(64) void chain_stats_kernel(const double* __restrict__ x, long long chains, long long draws_stride,
                                                          int dim, long long t0, long long n, int lag0, int nslab,
-                                                         int chain_blocks, double* __restrict__ partial) {
+                                                         int chain_blocks, long long first_chain, long long per, long long g0,
+                                                         double* __restrict__ partial) {
     const int lane = static_cast<int>(threadIdx.x);
     const int slab = static_cast<int>(blockIdx.x) % nslab;
-    const int cb = static_cast<int>(blockIdx.x) / nslab;
+    const int gcb = static_cast<int>(blockIdx.x) / nslab;   // (group, chain block): the order of the partials
+    const int cb = gcb % chain_blocks;
+    // the chains of this block's group inside the trace block: the job's chains [g * per, (g + 1) * per), counted from
+    // first_chain and clipped to [0, chains). All of it is the same in every lane (scalars, computed once per block).
+    const long long g = g0 + gcb / chain_blocks;
+    long long c_lo = g * per - first_chain, c_hi = c_lo + per;
+    if (c_lo < 0) c_lo = 0;
+    if (c_hi > chains) c_hi = chains;
     const int j = slab * 64 + lane;             // this lane's dimension
     const bool live = j < dim;
     double s_mean = 0.0, s_mean_sq = 0.0, s_var = 0.0;
@@ -38,7 +52,7 @@ __global__ __launch_bounds__(64) void chain_stats_kernel(const double* __restric
     for (int k = 0; k < kDiagLags; ++k) s_acov[k] = 0.0;
     const double inv_n = 1.0 / static_cast<double>(n);
 
-    for (long long c = cb; c < chains; c += chain_blocks) {
+    for (long long c = c_lo + cb; c < c_hi; c += chain_blocks) {
         const double* base = x + (c * draws_stride + t0) * dim + j;
         // ---- pass 1: mean (16 independent loads in flight)
         double acc[4] = {0.0, 0.0, 0.0, 0.0};
@@ -56,11 +70,9 @@ __global__ __launch_bounds__(64) void chain_stats_kernel(const double* __restric
         double acov[kDiagLags];
 #pragma unroll
         for (int k = 0; k < kDiagLags; ++k) acov[k] = 0.0;
-        double w[kDiagLags];   // delayed stream, previous block: centred x at t = b*16 - lag0 - 16 + i
+        double w[kDiagLags];   // delayed stream, previous block: centred x at t = b*16 - lag0 - 16 + i (before block 0: zeros)
 #pragma unroll
         for (int i = 0; i < kDiagLags; ++i) w[i] = 0.0;
-        if (lag0 > 0) {        // the block of the delayed stream that precedes block 0 lies at t < 0: zeros
-        }
         for (long long b = 0; b < n; b += kDiagLags) {
             double cur[kDiagLags], e[kDiagLags];   // e: delayed stream, current block: centred x at t = b - lag0 + i
 #pragma unroll
@@ -95,7 +107,7 @@ __global__ __launch_bounds__(64) void chain_stats_kernel(const double* __restric
 #pragma unroll
         for (int k = 0; k < kDiagLags; ++k) s_acov[k] += acov[k] * inv_n;   // biased (1/n) autocovariance
     }
-    double* out = partial + (static_cast<long long>(cb) * nslab + slab) * kDiagRows * 64 + lane;
+    double* out = partial + (static_cast<long long>(gcb) * nslab + slab) * kDiagRows * 64 + lane;
     out[0] = s_mean;
     out[64] = s_mean_sq;
     out[128] = s_var;
@@ -103,16 +115,18 @@ __global__ __launch_bounds__(64) void chain_stats_kernel(const double* __restric
     for (int k = 0; k < kDiagLags; ++k) out[(3 + k) * 64] = s_acov[k];
 }
 
-// out[row][dim] = sum over chain blocks, in block order (deterministic)
+// out[group][row][dim] = sum over the group's chain blocks, in block order (deterministic)
 __global__ void chain_stats_reduce_kernel(const double* __restrict__ partial, int nslab, int chain_blocks, int dim,
-                                          double* __restrict__ out) {
-    const int idx = static_cast<int>(blockIdx.x) * static_cast<int>(blockDim.x) + static_cast<int>(threadIdx.x);
-    if (idx >= kDiagRows * dim) return;
-    const int row = idx / dim, j = idx % dim;
+                                          long long groups, double* __restrict__ out) {
+    const long long idx = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
+    const long long block = static_cast<long long>(kDiagRows) * dim;   // one group's statistics block
+    if (idx >= groups * block) return;
+    const long long gi = idx / block;
+    const int row = static_cast<int>((idx % block) / dim), j = static_cast<int>(idx % dim);
     const int slab = j / 64, lane = j % 64;
     double acc = 0.0;
     for (int cb = 0; cb < chain_blocks; ++cb)
-        acc += partial[((static_cast<long long>(cb) * nslab + slab) * kDiagRows + row) * 64 + lane];
+        acc += partial[(((gi * chain_blocks + cb) * nslab + slab) * kDiagRows + row) * 64 + lane];
     out[idx] = acc;
 }
 
@@ -121,26 +135,46 @@ __global__ void chain_stats_reduce_kernel(const double* __restrict__ partial, in
 extern "C" int lmc_diag_lags_per_pass(void) { return lmc::kDiagLags; }
 
 // See include/lmc_hip.h. x and out are DEVICE pointers on the current device; the work is enqueued on `stream`.
-extern "C" int lmc_diag_chain_stats(const double* x, int64_t chains, int64_t draws_stride, int32_t dim, int64_t t0, int64_t n,
-                                    int32_t lag0, double* out, void* stream) {
+extern "C" int lmc_diag_chain_stats_grouped(const double* x, int64_t chains, int64_t draws_stride, int32_t dim, int64_t t0,
+                                            int64_t n, int32_t lag0, int64_t first_chain, int64_t chains_per_group, double* out,
+                                            void* stream) {
     using namespace lmc;
+    const int64_t lim = int64_t(1) << 31;
     if (!x || !out || chains < 1 || dim < 1 || n < 2 || t0 < 0 || t0 + n > draws_stride || lag0 < 0) return LMC_ERR_INVALID;
+    if (first_chain < 0 || chains_per_group < 1 || chains >= lim || first_chain >= lim || first_chain + chains >= lim)
+        return LMC_ERR_INVALID;
+    const int64_t per = chains_per_group < lim ? chains_per_group : lim - 1;   // (no job chain has an index >= 2^31: the same groups)
+    int64_t g0 = 0, g1 = 0;                             // the groups of the block's first and last chain
+    if (lmc_target_param_row(0, first_chain, per, &g0) != LMC_OK || lmc_target_param_row(chains - 1, first_chain, per, &g1) != LMC_OK)
+        return LMC_ERR_INVALID;
+    const int64_t groups = g1 - g0 + 1;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int nslab = (dim + 63) / 64;
-    long long cbl = 4096 / nslab;                       // ~16 wavefronts per CU, each looping over chains
+    long long cbl = (4096 / nslab) / groups;            // ~16 wavefronts per CU, each looping over chains: shared by the groups
+    if (cbl > per) cbl = per;
     if (cbl > chains) cbl = chains;
     if (cbl < 1) cbl = 1;
     const int chain_blocks = static_cast<int>(cbl);
+    const long long blocks = groups * chain_blocks * nslab;
+    const long long total = groups * kDiagRows * dim;
+    if (blocks >= lim || (total + 255) / 256 >= lim) return LMC_ERR_INVALID;
     double* partial = nullptr;
-    const size_t bytes = static_cast<size_t>(chain_blocks) * nslab * kDiagRows * 64 * sizeof(double);
+    const size_t bytes = static_cast<size_t>(blocks) * kDiagRows * 64 * sizeof(double);
     if (hipMallocAsync(reinterpret_cast<void**>(&partial), bytes, s) != hipSuccess) return LMC_ERR_HIP;
     (void)hipGetLastError();
-    hipLaunchKernelGGL(chain_stats_kernel, dim3(chain_blocks * nslab), dim3(64), 0, s, x, static_cast<long long>(chains),
+    hipLaunchKernelGGL(chain_stats_kernel, dim3(static_cast<unsigned>(blocks)), dim3(64), 0, s, x, static_cast<long long>(chains),
                        static_cast<long long>(draws_stride), dim, static_cast<long long>(t0), static_cast<long long>(n), lag0,
-                       nslab, chain_blocks, partial);
-    const int total = kDiagRows * dim;
-    hipLaunchKernelGGL(chain_stats_reduce_kernel, dim3((total + 255) / 256), dim3(256), 0, s, partial, nslab, chain_blocks, dim, out);
+                       nslab, chain_blocks, static_cast<long long>(first_chain), static_cast<long long>(per),
+                       static_cast<long long>(g0), partial);
+    hipLaunchKernelGGL(chain_stats_reduce_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, s, partial, nslab,
+                       chain_blocks, dim, static_cast<long long>(groups), out);
     const hipError_t err = hipGetLastError();
     (void)hipFreeAsync(partial, s);
     return err == hipSuccess ? LMC_OK : LMC_ERR_HIP;
+}
+
+// One group that holds every chain of the block.
+extern "C" int lmc_diag_chain_stats(const double* x, int64_t chains, int64_t draws_stride, int32_t dim, int64_t t0, int64_t n,
+                                    int32_t lag0, double* out, void* stream) {
+    return lmc_diag_chain_stats_grouped(x, chains, draws_stride, dim, t0, n, lag0, 0, chains, out, stream);
 }

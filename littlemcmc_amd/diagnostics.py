@@ -13,7 +13,10 @@ Everything reduces to per-dimension *sufficient statistics that add over chains*
 For draws in HBM (``Engine.trace_device_ptr()`` through ``trace_tensor``) they come from the HIP kernel
 ``lmc_diag_chain_stats`` (csrc/lmc_diag.hip), 16 lags per pass over the trace; passes continue until Geyer's initial
 positive sequence has ended in every dimension (one pass for well-mixing NUTS chains), each pass followed by ONE
-small all-reduce (RCCL on GPUs) of its (3 + 16) x d block. There is one backend: the HIP kernel. The reduction /
+small all-reduce (RCCL on GPUs) of its (3 + 16) x d block. ``chains_per_group=per`` (a ``targets.Batched`` job: many
+posteriors, ``per`` consecutive chains each) gives every statistic and every result a leading group axis from the same
+passes -- ``lmc_diag_chain_stats_grouped``, one launch for all groups and still one host look per pass. There is one
+backend: the HIP kernel. The reduction /
 finalisation logic above it is backend-agnostic tensor code, and the CPU tests of that logic (gloo, world_size 2) inject
 the test oracle's restatement of the kernel's block (oracle/diagnostics_oracle.py: torch_chain_stats) through the
 ``stats_fn`` argument; nothing in this package computes the statistics on the host."""
@@ -32,21 +35,25 @@ def split_chains(x):
     return torch.cat([x[:, :h], x[:, n - h:]], dim=0)
 
 
-def _hip_chain_stats(x, t0, n, lag0):
+def _hip_chain_stats(x, t0, n, lag0, first_chain=None, per=None):
     """One pass of lmc_diag_chain_stats over x[chains, draws, d] (float64, contiguous, on a ROCm device):
-    -> [3 + 16, d] float64 tensor on the same device."""
+    -> [3 + 16, d] float64 tensor on the same device. With ``per`` chains per group, x's chain 0 being chain ``first_chain`` of
+    the job, one pass of lmc_diag_chain_stats_grouped: -> [groups touched, 3 + 16, d]."""
     from . import _abi
 
     lib = _abi.load()
     c, _n, d = x.shape
     stride = x.stride(0) // d if c > 1 else _n     # rows of a chain lie d apart; chains `stride` rows apart (_row_major)
-    out = torch.empty((3 + LAGS_PER_PASS, d), dtype=torch.float64, device=x.device)
+    name, grouping, lead = "lmc_diag_chain_stats", (), ()
+    if per is not None:
+        name, grouping, lead = "lmc_diag_chain_stats_grouped", (int(first_chain), int(per)), (_touched(first_chain, c, per)[1],)
+    out = torch.empty(lead + (3 + LAGS_PER_PASS, d), dtype=torch.float64, device=x.device)
     with torch.cuda.device(x.device):
         stream = torch.cuda.current_stream(x.device).cuda_stream
-        rc = lib.lmc_diag_chain_stats(ctypes.c_void_p(x.data_ptr()), c, stride, d, int(t0), int(n), int(lag0),
-                                      ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(stream))
+        rc = getattr(lib, name)(ctypes.c_void_p(x.data_ptr()), c, stride, d, int(t0), int(n), int(lag0), *grouping,
+                                ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(stream))
     if rc != 0:
-        raise RuntimeError("lmc_diag_chain_stats failed (status %d)" % rc)
+        raise RuntimeError("%s failed (status %d)" % (name, rc))
     return out
 
 
@@ -63,14 +70,68 @@ def _blocks(x):
     return list(x) if isinstance(x, (list, tuple)) else [x]
 
 
-def chain_stats_pass(x, ranges, lag0, stats_fn=None):
+def _touched(first_chain, chains, per):
+    """(g0, number of groups) that the job's chains [first_chain, first_chain + chains) touch, ``per`` chains a group."""
+    g0 = first_chain // per
+    return g0, (first_chain + chains - 1) // per - g0 + 1
+
+
+def chain_stats_pass(x, ranges, lag0, stats_fn=None, chains_per_group=None, first_chain=0):
+    """Statistics block of one pass: [3 + 16, d], or with ``chains_per_group`` [groups touched, 3 + 16, d] -- x's chain 0 is
+    chain ``first_chain`` of the job, and a first or last group that lies only partly in x holds the sums over its chains
+    that are present. A list of blocks (in job order) is added up: a group that straddles two blocks is the sum of its parts."""
     if isinstance(x, (list, tuple)):   # one kernel per device, all enqueued before the first result is moved
+        if chains_per_group is not None:
+            per, firsts = int(chains_per_group), [int(first_chain)]
+            for b in x:
+                firsts.append(firsts[-1] + int(b.shape[0]))
+            parts = [(f, chain_stats_pass(b, ranges, lag0, stats_fn, per, f)) for f, b in zip(firsts, x) if b.shape[0] > 0]
+            g0, touched = _touched(firsts[0], max(firsts[-1] - firsts[0], 1), per)
+            tot = torch.zeros((touched, 3 + LAGS_PER_PASS, int(x[0].shape[2])), dtype=torch.float64, device=x[0].device)
+            for f, p_ in parts:
+                off = f // per - g0
+                tot[off:off + p_.shape[0]] += p_.to(tot.device)
+            return tot
         parts = [chain_stats_pass(b, ranges, lag0, stats_fn) for b in x]
         tot = parts[0]
         for p_ in parts[1:]:
             tot = tot + p_.to(tot.device)
         return tot
+    if chains_per_group is not None:
+        return _chain_stats_pass_grouped(x, ranges, lag0, stats_fn, int(chains_per_group), int(first_chain))
     return _chain_stats_pass_one(x, ranges, lag0, stats_fn)
+
+
+def _device_block(x):
+    """x as the HIP kernel reads it (float64, _row_major), or HipLibraryError for a CPU tensor."""
+    if not x.is_cuda:
+        from ._abi import HipLibraryError
+
+        raise HipLibraryError("diagnostics run on draws in HBM (a ROCm tensor, e.g. diagnostics.trace_tensor(engine)); "
+                              "got a CPU tensor and there is no host implementation")
+    if x.dtype != torch.float64 or not _row_major(x):
+        x = x.to(torch.float64).contiguous()
+    return x
+
+
+def _chain_stats_pass_grouped(x, ranges, lag0, stats_fn, per, first_chain):
+    """[groups touched, 3 + 16, d] of one block. With ``stats_fn`` (tests of the logic) every touched group's chains are
+    handed to it as one slice; without, the HIP kernel does all groups in one launch per range."""
+    if per < 1 or first_chain < 0:
+        raise ValueError("chains_per_group must be >= 1 and first_chain >= 0 (got %d, %d)" % (per, first_chain))
+    c = int(x.shape[0])
+    if c == 0:
+        return torch.zeros((0, 3 + LAGS_PER_PASS, x.shape[2]), dtype=torch.float64, device=x.device)
+    g0, touched = _touched(first_chain, c, per)
+    if stats_fn is not None:
+        cuts = [min(max((g0 + i) * per - first_chain, 0), c) for i in range(touched + 1)]
+        return torch.stack([_chain_stats_pass_one(x[lo:hi], ranges, lag0, stats_fn) for lo, hi in zip(cuts[:-1], cuts[1:])])
+    x = _device_block(x)
+    tot = None
+    for t0, n in ranges:
+        blk = _hip_chain_stats(x, t0, n, lag0, first_chain, per)
+        tot = blk if tot is None else tot + blk
+    return tot
 
 
 def _chain_stats_pass_one(x, ranges, lag0, stats_fn=None):
@@ -81,13 +142,7 @@ def _chain_stats_pass_one(x, ranges, lag0, stats_fn=None):
         return torch.zeros((3 + LAGS_PER_PASS, x.shape[2]), dtype=torch.float64, device=x.device)
     fn = stats_fn
     if fn is None:
-        if not x.is_cuda:
-            from ._abi import HipLibraryError
-
-            raise HipLibraryError("diagnostics run on draws in HBM (a ROCm tensor, e.g. diagnostics.trace_tensor(engine)); "
-                                  "got a CPU tensor and there is no host implementation")
-        if x.dtype != torch.float64 or not _row_major(x):
-            x = x.to(torch.float64).contiguous()
+        x = _device_block(x)
         fn = _hip_chain_stats
     tot = None
     for t0, n in ranges:
@@ -116,30 +171,47 @@ def _all_reduce(t, group=None, reduce_device=None, op="sum"):
 
 
 def _geyer_ended(stats):
-    """True when the initial positive sequence has ended within the available lags in every dimension."""
+    """True when the initial positive sequence has ended within the available lags in every dimension (of every group:
+    the lag axis is the last but one, whatever leads)."""
     m, n = float(stats["n_chains"]), float(stats["n_draws"])
     w = stats["sum_var"] / m
     gmean = stats["sum_mean"] / m
     b_over_n = (stats["sum_mean_sq"] - m * gmean ** 2) / (m - 1.0) if m > 1 else torch.zeros_like(w)
     var_plus = w * (n - 1.0) / n + b_over_n
     acov = stats["sum_acov"] / m
-    rho = 1.0 - (w[None, :] - acov * (n / (n - 1.0))) / var_plus[None, :]
-    rho[0] = 1.0
-    T = rho.shape[0] - (rho.shape[0] % 2)
-    pairs = rho[0:T:2] + rho[1:T:2]
-    return bool(((pairs <= 0).any(dim=0) | ~torch.isfinite(pairs).all(dim=0)).all())
+    rho = 1.0 - (w.unsqueeze(-2) - acov * (n / (n - 1.0))) / var_plus.unsqueeze(-2)
+    rho[..., 0, :] = 1.0
+    T = rho.shape[-2] - (rho.shape[-2] % 2)
+    pairs = rho[..., 0:T:2, :] + rho[..., 1:T:2, :]
+    return bool(((pairs <= 0).any(dim=-2) | ~torch.isfinite(pairs).all(dim=-2)).all())
 
 
-def sufficient_stats(x, split=True, max_lag=None, group=None, reduce_device=None, stats_fn=None):
+def _chains_per_group(chains, chains_per_group, group=None):
+    """``chains_per_group`` as an int, checked against the job's chain total; grouped diagnostics are a one-process matter."""
+    per = int(chains_per_group)
+    if _group_active(group):
+        raise ValueError("chains_per_group with an active process group: targets.Batched does not run under "
+                         "sample_distributed, and grouped diagnostics are not reduced across ranks")
+    if per < 1 or chains < per or chains % per != 0:
+        raise ValueError("chains_per_group=%d needs a multiple of %d chains (got chains=%d)" % (per, max(per, 1), chains))
+    return per
+
+
+def sufficient_stats(x, split=True, max_lag=None, group=None, reduce_device=None, stats_fn=None, chains_per_group=None):
     """Reduced (over chains, halves and ranks) sufficient statistics of x[chains, draws, d] (this rank's block, or the
     list of this process's per-GPU blocks). Every quantity that steers the pass loop -- the draw count, the lag limit,
     "Geyer's sequence has ended" -- is a REDUCED one, so all ranks issue the same collectives whatever their blocks hold
-    (a rank may own no chain at all)."""
+    (a rank may own no chain at all).
+
+    ``chains_per_group=per``: the job's chains (the blocks, in job order) are G = chains / per posteriors of ``per``
+    consecutive chains; every statistic gets a leading [G] axis, ``n_chains`` is the chains (times halves) of ONE group, and
+    the passes continue until Geyer's sequence has ended in every dimension of every group -- still one host look per pass."""
     blocks = _blocks(x)
     held = [b for b in blocks if b.shape[0] > 0]
     if len({int(b.shape[1]) for b in held}) > 1:
         raise ValueError("the chain blocks hold different numbers of draws per chain: %s" % [int(b.shape[1]) for b in held])
     c = sum(int(b.shape[0]) for b in blocks)
+    per = None if chains_per_group is None else _chains_per_group(c, chains_per_group, group)
     n_all, d = (held[0].shape[1], held[0].shape[2]) if held else (blocks[0].shape[1], blocks[0].shape[2])
     dev = blocks[0].device
     if len(blocks) > 1:
@@ -164,17 +236,20 @@ def sufficient_stats(x, split=True, max_lag=None, group=None, reduce_device=None
     if n < 4:
         raise ValueError("need at least %d draws per chain" % (4 * halves))
     limit = n if max_lag is None else min(int(max_lag), n)
-    nch = _all_reduce(torch.tensor([float(c * halves)], dtype=torch.float64, device=dev), group, reduce_device)
+    nch = _all_reduce(torch.tensor([float((c if per is None else per) * halves)], dtype=torch.float64, device=dev), group,
+                      reduce_device)
     stats = {"n_chains": nch[0], "n_draws": torch.tensor(float(n), dtype=torch.float64, device=dev)}
+    if per is not None:
+        stats["groups"] = c // per
     acov_blocks = []
     lag0 = 0
     while True:
-        blk = _all_reduce(chain_stats_pass(x, ranges, lag0, stats_fn), group, reduce_device)   # the pass's one collective
+        blk = _all_reduce(chain_stats_pass(x, ranges, lag0, stats_fn, per), group, reduce_device)   # the pass's one collective
         if lag0 == 0:
-            stats["sum_mean"], stats["sum_mean_sq"], stats["sum_var"] = blk[0], blk[1], blk[2]
-        acov_blocks.append(blk[3:])
+            stats["sum_mean"], stats["sum_mean_sq"], stats["sum_var"] = blk[..., 0, :], blk[..., 1, :], blk[..., 2, :]
+        acov_blocks.append(blk[..., 3:, :])
         lag0 += LAGS_PER_PASS
-        stats["sum_acov"] = torch.cat(acov_blocks, dim=0)[:limit]
+        stats["sum_acov"] = torch.cat(acov_blocks, dim=-2)[..., :limit, :]
         if lag0 >= limit:
             break
         ended = torch.tensor([1.0 if _geyer_ended(stats) else 0.0], dtype=torch.float64, device=dev)
@@ -187,7 +262,8 @@ def sufficient_stats(x, split=True, max_lag=None, group=None, reduce_device=None
 
 
 def finalize(stats):
-    """R-hat[d] and ESS[d] from (reduced) sufficient statistics."""
+    """R-hat[d] and ESS[d] from (reduced) sufficient statistics; [G, d] each, plus rhat_max[G], ess_min[G] and ``groups``,
+    from grouped ones (sufficient_stats(..., chains_per_group=)): the lag axis is the last but one, whatever leads."""
     m = float(stats["n_chains"])
     n = float(stats["n_draws"])
     w = stats["sum_var"] / m                                              # mean within-chain variance
@@ -199,24 +275,27 @@ def finalize(stats):
     var_plus = w * (n - 1.0) / n + b_over_n
     rhat = torch.sqrt(var_plus / w)
     acov = stats["sum_acov"] / m                                          # [T, d]
-    rho = 1.0 - (w[None, :] - acov * (n / (n - 1.0))) / var_plus[None, :]
-    rho[0] = 1.0
-    T, d = rho.shape
+    rho = 1.0 - (w.unsqueeze(-2) - acov * (n / (n - 1.0))) / var_plus.unsqueeze(-2)
+    rho[..., 0, :] = 1.0
+    T = rho.shape[-2]
     if T % 2:
-        rho = rho[:-1]
+        rho = rho[..., :-1, :]
         T -= 1
-    pairs = rho[0::2] + rho[1::2]                                         # Geyer P_t, [T/2, d]
-    positive = torch.cumprod((pairs > 0).to(pairs.dtype), dim=0)          # initial positive sequence
+    pairs = rho[..., 0::2, :] + rho[..., 1::2, :]                         # Geyer P_t, [T/2, d]
+    positive = torch.cumprod((pairs > 0).to(pairs.dtype), dim=-2)         # initial positive sequence
     pairs = torch.nan_to_num(pairs, nan=0.0) * positive
-    pairs = torch.cummin(pairs, dim=0).values                             # initial monotone sequence
-    tau = -1.0 + 2.0 * pairs.sum(dim=0)
+    pairs = torch.cummin(pairs, dim=-2).values                            # initial monotone sequence
+    tau = -1.0 + 2.0 * pairs.sum(dim=-2)
     tau = torch.clamp(tau, min=1.0 / math.log10(max(m * n, 10.0)))
     ess = m * n / tau
-    return {"rhat": rhat, "ess": ess, "mean": gmean, "var": var_plus, "n_chains": m, "n_draws": n,
-            "lag_passes": stats.get("lag_passes", 0)}
+    out = {"rhat": rhat, "ess": ess, "mean": gmean, "var": var_plus, "n_chains": m, "n_draws": n,
+           "lag_passes": stats.get("lag_passes", 0)}
+    if "groups" in stats:   # "which of my posteriors has not converged" is one comparison
+        out.update(groups=stats["groups"], rhat_max=rhat.max(dim=-1).values, ess_min=ess.min(dim=-1).values)
+    return out
 
 
-def rank_normalize(x, chunk_dims=8, group=None, reduce_device=None):
+def rank_normalize(x, chunk_dims=8, group=None, reduce_device=None, chains_per_group=None):
     """z-scores of the pooled ranks of every dimension (Vehtari et al. 2021, eq. 14): z = Phi^-1((r - 3/8) / (S + 1/4)),
     S = ALL chains x draws of ALL ranks, r = the average rank of the draw among them (ties -- a rejected HMC proposal, a
     NUTS tree that returns its start point -- share the mean of their positions, scipy's rankdata(method="average")).
@@ -224,9 +303,15 @@ def rank_normalize(x, chunk_dims=8, group=None, reduce_device=None):
     Multi-GPU: the ranks are global. Every rank sorts its own pooled draws of a block of dimensions, the sorted blocks
     are all-gathered (padded to the largest block with +inf), and a draw's global rank is the sum over ranks of its
     insertion points: r = #less + (#equal + 1) / 2. Normalising each rank's block on its own would map every block to
-    N(0, 1) separately and erase exactly the between-rank differences R-hat is there to detect."""
+    N(0, 1) separately and erase exactly the between-rank differences R-hat is there to detect.
+
+    ``chains_per_group=per``: the ranks are taken within each group of ``per`` consecutive chains (S = per x draws), all
+    groups sorted in one call per chunk of dimensions. A list of blocks is taken block by block, which needs every group
+    to lie inside one block."""
     import torch.distributed as dist
 
+    if chains_per_group is not None:
+        return _rank_normalize_grouped(x, chunk_dims, group, chains_per_group)
     if isinstance(x, (list, tuple)):
         return _rank_normalize_blocks(list(x), chunk_dims, group)
     c, n, d = x.shape
@@ -271,6 +356,36 @@ def rank_normalize(x, chunk_dims=8, group=None, reduce_device=None):
     return out
 
 
+def _rank_normalize_grouped(x, chunk_dims, group, chains_per_group):
+    """rank_normalize within groups of ``chains_per_group`` consecutive chains: one batched sort [G, k, per * n] per chunk of k
+    dimensions, ties averaged as in the ungrouped form. Like that form it holds about six temporaries of chains x draws x k
+    values (8 bytes each: float64 and the int64 insertion points) per chunk on the device -- 0.5 GB each at 16 384 chains x
+    500 draws and k = 8; ``chunk_dims`` is the knob (call rank_normalize(x, chunk_dims=1, chains_per_group=per) and summarize
+    its result when HBM is nearly full)."""
+    if isinstance(x, (list, tuple)):
+        per = _chains_per_group(sum(int(b.shape[0]) for b in x), chains_per_group, group)
+        if any(int(b.shape[0]) % per for b in x):
+            raise ValueError("rank_normalize(chains_per_group=%d): a group straddles two chain blocks (blocks of %s chains); "
+                             "ranks within a group need the group's draws on one device"
+                             % (per, [int(b.shape[0]) for b in x]))
+        return [_rank_normalize_grouped(b, chunk_dims, group, per) if b.shape[0] else b.to(torch.float64) for b in x]
+    c, n, d = x.shape
+    per = _chains_per_group(c, chains_per_group, group)
+    groups, S = c // per, per * n
+    out = torch.empty((c, n, d), dtype=torch.float64, device=x.device)
+    for lo in range(0, d, chunk_dims):
+        hi = min(lo + chunk_dims, d)
+        blk = x[:, :, lo:hi].reshape(groups, S, hi - lo).to(torch.float64).transpose(1, 2).contiguous()   # [G, k, S]
+        srt = torch.sort(blk, dim=2).values
+        less = torch.searchsorted(srt, blk, right=False).to(torch.float64)
+        leq = torch.searchsorted(srt, blk, right=True).to(torch.float64)
+        ranks = less + 0.5 * (leq - less + 1.0)
+        p = (ranks - 0.375) / (S + 0.25)
+        z = math.sqrt(2.0) * torch.erfinv(2.0 * p - 1.0)
+        out[:, :, lo:hi] = z.transpose(1, 2).reshape(c, n, hi - lo)
+    return out
+
+
 def _rank_normalize_blocks(blocks, chunk_dims, group):
     """rank_normalize for the per-GPU chain blocks of one process: global ranks over ALL blocks. Every device sorts its
     own block of a chunk of dimensions; every device then counts its draws' insertion points in every sorted pool
@@ -305,28 +420,40 @@ def _rank_normalize_blocks(blocks, chunk_dims, group):
 
 
 def summarize(x, split=True, max_lag=None, group=None, reduce_device=None, rank_normalized=False, chunk=None,
-              stats_fn=None):
+              stats_fn=None, chains_per_group=None):
     """x[chains, draws, d] (this rank's chain block; or the list of this process's per-GPU blocks, trace_tensor(group))
     -> dict(rhat[d], ess[d], mean[d], var[d]) over ALL chains of ALL ranks.
     ``rank_normalized=True``: the rank-normalised split-R-hat / bulk ESS (diagnostics of the z-scores of the GLOBAL
-    ranks). ``stats_fn`` replaces the HIP kernel (tests of the reduction logic only)."""
+    ranks). ``stats_fn`` replaces the HIP kernel (tests of the reduction logic only).
+    ``chains_per_group=per`` (a ``targets.Batched`` job; ``Batched.summarize`` fills it in): one posterior per ``per``
+    consecutive chains, all of them in the same passes -> rhat[G, d], ess[G, d], mean[G, d], var[G, d], rhat_max[G],
+    ess_min[G], groups; n_chains counts the chains (halves) of one group. Not with a process group."""
     if rank_normalized:
-        x = rank_normalize(x, group=group, reduce_device=reduce_device)
+        x = rank_normalize(x, group=group, reduce_device=reduce_device, chains_per_group=chains_per_group)
     out = finalize(sufficient_stats(x, split=split, max_lag=max_lag, group=group, reduce_device=reduce_device,
-                                    stats_fn=stats_fn))
+                                    stats_fn=stats_fn, chains_per_group=chains_per_group))
     out["definition"] = ("rank-normalised " if rank_normalized else "") + (
         "split-R-hat / Geyer initial-monotone-sequence ESS" if split else "R-hat / Geyer initial-monotone-sequence ESS")
     return out
 
 
-def rhat_from_moments(mean, m2, n, group=None, reduce_device=None):
+def rhat_from_moments(mean, m2, n, group=None, reduce_device=None, chains_per_group=None):
     """(Non-split) R-hat[d] from per-chain running moments -- mean[chains, d], m2[chains, d] (sum of squared
     deviations), n[chains] equal draws per chain -- reduced over ranks with one all-reduce of
-    {chains, draws, sum mean, sum mean^2, sum var}. This is the trace-free diagnostic of SURVEY.md section 8e."""
+    {chains, draws, sum mean, sum mean^2, sum var}. This is the trace-free diagnostic of SURVEY.md section 8e.
+    ``chains_per_group=per``: R-hat[G, d], one row per ``per`` consecutive chains (not with a process group)."""
     mean = torch.as_tensor(mean, dtype=torch.float64)
     m2 = torch.as_tensor(m2, dtype=torch.float64)
     nt = torch.as_tensor(n).to(torch.float64)
     d = mean.shape[1]
+    if chains_per_group is not None:
+        per = _chains_per_group(int(mean.shape[0]), chains_per_group, group)
+        nd, m = float(nt.mean()), float(per)
+        mean, m2 = mean.reshape(-1, per, d), m2.reshape(-1, per, d)
+        w = (m2 / (nd - 1.0)).sum(dim=1) / m
+        gmean = mean.sum(dim=1) / m
+        b_over_n = ((mean ** 2).sum(dim=1) - m * gmean ** 2) / (m - 1.0) if per > 1 else torch.zeros_like(w)
+        return torch.sqrt((w * (nd - 1.0) / nd + b_over_n) / w)
     nd_local = float(nt.mean()) if nt.numel() else 2.0
     blk = torch.zeros((3, d), dtype=torch.float64, device=mean.device)
     head = torch.zeros((2,), dtype=torch.float64, device=mean.device)

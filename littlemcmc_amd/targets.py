@@ -590,8 +590,9 @@ class Batched(DeviceTarget):
     pick a chain's row where they call the functor's ``init``), ``groups`` is G, ``members`` the list; ``batched[g]`` is member g
     and ``len(batched)`` is G. A ``Batched`` cannot be called with one point -- a point has no group: call ``batched[g](q)``.
 
-    Diagnostics are per posterior: take R-hat / ESS over ``trace[sl]`` for ``sl`` in ``chain_slices(chains)``. R-hat ACROSS
-    groups is meaningless -- the groups' chains target different distributions and are supposed to disagree."""
+    Diagnostics are per posterior: ``batched.summarize(x)`` gives R-hat / ESS ``[G, d]`` of all groups in one pass over the
+    draws in HBM (``trace[sl]`` for ``sl`` in ``chain_slices(chains)`` are the chains of one group). R-hat ACROSS groups is
+    meaningless -- the groups' chains target different distributions and are supposed to disagree."""
 
     def __init__(self, members):
         members = list(members)
@@ -670,6 +671,14 @@ class Batched(DeviceTarget):
         posterior -- what R-hat / ESS are taken over (across groups they are meaningless)."""
         per = self.group_size(chains)
         return [slice(g * per, (g + 1) * per) for g in range(self.groups)]
+
+    def summarize(self, x, **kw):
+        """``diagnostics.summarize`` per posterior: x is the job's draws in HBM, one tensor [chains, draws, d] or the list of
+        per-GPU blocks from ``diagnostics.trace_tensor(engine_group)`` -> rhat[G, d], ess[G, d], rhat_max[G], ess_min[G], ..."""
+        from . import diagnostics
+
+        chains = sum(int(b.shape[0]) for b in x) if isinstance(x, (list, tuple)) else int(x.shape[0])
+        return diagnostics.summarize(x, chains_per_group=self.group_size(chains), **kw)
 
     def __repr__(self):
         return "Batched(%d x %s, d=%d)" % (self.groups, type(self.members[0]).__name__, self.d)
