@@ -673,6 +673,35 @@ int lmc_diag_chain_stats(const double* x, int64_t chains, int64_t draws_stride, 
 int lmc_diag_chain_stats_grouped(const double* x, int64_t chains, int64_t draws_stride, int32_t dim, int64_t t0, int64_t n,
                                  int32_t lag0, int64_t first_chain, int64_t chains_per_group, double* out, void* stream);
 
+/* ---- pointwise predictive pass over the draws in HBM, GLM family (additive within ABI 9; littlemcmc_amd/predictive.py:
+ * lppd, WAIC, held-out scoring) ------------------------------------------------------------------------------------------
+ * x, chains, draws_stride, dim, t0, n: the trace block and sub-series of lmc_diag_chain_stats (a draw is dim contiguous
+ * doubles, chains lie draws_stride rows apart). rows is a DEVICE table [n_rows][row_len] of parameter rows in the
+ * LMC_TARGET_GLM layout -- the rows the chains were sampled with, or rows of held-out data of the same dim; chain c of the
+ * block belongs to group (first_chain + c) / chains_per_group (lmc_target_param_row) and is scored on that group's row. With
+ * l[s, i] the pointwise log-likelihood of draw s at observation i -- the l_n of LMC_TARGET_GLM above, constants dropped -- and
+ * the block touching groups g0 .. g1, out is [g1 - g0 + 1][6][npad] doubles (DEVICE), npad that of the rows; per group and
+ * observation, over the n_g draws of the group that lie in x, rows [t0, t0 + n):
+ *   [0] n_g (as a double)   [1] m = max_s l   [2] S = sum_s exp(l - m)   [3] mean_s l   [4] M2 = sum_s (l - mean)^2
+ *   [5] sum_s mu, mu the mean response: sigmoid(eta) (bernoulli), exp(eta) (poisson), eta (gaussian)
+ * so that log mean_s exp(l) = m + log S - log n_g. Two blocks a, b of draws merge by m = max(ma, mb),
+ * S = Sa exp(ma - m) + Sb exp(mb - m), Chan's update mean = mean_a + (mean_b - mean_a) nb / n,
+ * M2 = M2a + M2b + (mean_b - mean_a)^2 na nb / n, sums for [0] and [5]; a block of count 0 is skipped by its count. A group
+ * that lies only partly in x gets the block of its draws that are present; the parts merge by the same rule (two GPUs).
+ * Observations i >= N (padding up to npad) hold finite values of no meaning. Bit-reproducible: no floating-point atomics,
+ * chain blocks merged in a fixed order.
+ * Non-finite l: a draw with l = -inf (the poisson exp(eta) overflowed) counts in [0] and contributes exp(l - m) := 0 to S
+ * whatever m is, so [1] and [2] are those of the other draws and m + log S stays finite (every draw -inf: m = -inf, S = 0);
+ * [3] and [4] are then non-finite (-inf or NaN) and [5] is +inf. A NaN l makes [1] .. [5] of that observation NaN.
+ * Refused with LMC_ERR_INVALID before any HIP call: NULL x, rows or out; what lmc_diag_chain_stats_grouped refuses for
+ * chains, dim, t0, first_chain and chains_per_group; n < 1 or t0 + n > draws_stride (one draw is a block like any other:
+ * nothing here divides by n - 1); dim > LMC_GLM_MAX_DIM; a row_len that no N gives at that dim; a touched group >= n_rows.
+ * Then the headers of the touched rows are read back in one copy on `stream` (the call's one host look, before any launch),
+ * and a header that disagrees with dim or row_len or carries an unknown likelihood code is refused the same way. */
+int lmc_glm_pointwise(const double* x, int64_t chains, int64_t draws_stride, int32_t dim, int64_t t0, int64_t n,
+                      const double* rows, int64_t row_len, int64_t n_rows, int64_t first_chain, int64_t chains_per_group,
+                      double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -209,6 +209,32 @@ class GLM(DeviceTarget):
         cov = 0.5 * (cov + cov.T)
         return np.linalg.solve(prec, self.X.T @ self.y * self.isig2), cov
 
+    def loglik_constant(self, y=None):
+        """``const[N]``: what the pointwise log-likelihood ``l_n`` above drops, so that ``l_n + const_n`` is the normalised
+        log density of ``y_n`` (default: the target's own ``y``): 0 (bernoulli), ``-lgamma(y + 1)`` (poisson),
+        ``-log(sigma) - log(2 pi) / 2`` (gaussian)."""
+        import math
+
+        y = self.y if y is None else np.asarray(y, dtype=np.float64)
+        if self.likelihood == "poisson":
+            return np.array([-math.lgamma(float(v) + 1.0) for v in y], dtype=np.float64).reshape(y.shape)
+        if self.likelihood == "gaussian":
+            return np.full(y.shape, -math.log(self.sigma) - 0.5 * math.log(2.0 * math.pi))
+        return np.zeros(y.shape)
+
+    def pointwise_stats(self, x, **kw):
+        """``predictive.pointwise_stats(x, self, ...)``: the per-observation statistics of the draws ``x`` in HBM, ``[1, N]``."""
+        from . import predictive
+
+        return predictive.pointwise_stats(x, self, **kw)
+
+    def waic(self, x, **kw):
+        """``predictive.waic(x, self, ...)``: lppd / WAIC of the draws ``x`` in HBM (leading axis 1); ``data=(X_new, y_new)``
+        scores held-out points."""
+        from . import predictive
+
+        return predictive.waic(x, self, **kw)
+
     def __repr__(self):
         return "GLM(%s, N=%d, d=%d)" % (self.likelihood, self.n_obs, self.d)
 
@@ -679,6 +705,19 @@ class Batched(DeviceTarget):
 
         chains = sum(int(b.shape[0]) for b in x) if isinstance(x, (list, tuple)) else int(x.shape[0])
         return diagnostics.summarize(x, chains_per_group=self.group_size(chains), **kw)
+
+    def pointwise_stats(self, x, **kw):
+        """``predictive.pointwise_stats(x, self, ...)`` per posterior (GLM members): the per-observation statistics ``[G, N]``."""
+        from . import predictive
+
+        return predictive.pointwise_stats(x, self, **kw)
+
+    def waic(self, x, **kw):
+        """``predictive.waic(x, self, ...)`` per posterior (GLM members): lppd[G, N], elpd_waic[G], se[G], ... of all groups in
+        one pass over the draws in HBM; ``data=[(X_new, y_new), ...]`` scores a held-out fold per group."""
+        from . import predictive
+
+        return predictive.waic(x, self, **kw)
 
     def __repr__(self):
         return "Batched(%d x %s, d=%d)" % (self.groups, type(self.members[0]).__name__, self.d)
