@@ -11,6 +11,7 @@ from littlemcmc_amd import targets as T
 from oracle import lmc_oracle as orc
 from oracle import targets as OT
 from tests import _counter_model as cm
+from tests import _glm_oracle as GO
 from tests._gpu_util import INT_STATS, device_target
 
 pytestmark = pytest.mark.gpu
@@ -82,14 +83,22 @@ CASES = {
     "ar1_16_jitter": ("ar1", 16, 8, 40, 40, "nuts", {"jitter": (0.8, 1.2)}),   # k = 0 is drawn before the tree
     "std_normal_70_scaling": ("std_normal", 70, 8, 40, 20, "nuts", {"scaling": 1.3}),   # float64 momentum
     "user_std_normal_16": ("std_normal", 16, 8, 40, 40, "nuts", {"user": True}),        # run-time compiled density
+    # targets.GLM: family "glm" names a cell (N, d, likelihood) of tests/_glm_model.py instead of an oracle family
+    "glm_63_3_bernoulli": ("glm", 3, 8, 30, 30, "nuts", {"glm": (63, 3, "bernoulli")}),
+    "glm_130_130_poisson": ("glm", 130, 4, 20, 10, "nuts", {"glm": (130, 130, "poisson")}),   # NS = 4, divergences
 }
 _REPLAYED = {}
 
 
 def _steps(family, d, kind, extra, seeds):
     """(device step, factory of oracle steps, start)."""
-    f = OT.make(family, d)
-    tgt = T.UserTarget.separable(d, **_USER_STD_NORMAL) if extra.get("user") else device_target(family, d, f.params())
+    if "glm" in extra:   # the float64 statement of the posterior in the device's order, and the targets.GLM of the same cell
+        assert family == "glm" and extra["glm"][1] == d
+        f, make_target, _info = GO.oracle_glm(*extra["glm"])
+        tgt = make_target()
+    else:
+        f = OT.make(family, d)
+        tgt = T.UserTarget.separable(d, **_USER_STD_NORMAL) if extra.get("user") else device_target(family, d, f.params())
     jit = extra.get("jitter")
     start = orc.jitter_start(seeds[0], d)
     if kind == "hmc":
@@ -214,7 +223,8 @@ def test_every_iteration_replays_against_the_oracle(name):
     res = _replay(name)
     assert res["checked"] + res["fragile"] == res["total"]
     assert res["fragile"] <= max(1, res["total"] // 100), res
-    want_shape = {"ar1_200": (4, 1), "ar1_300": (4, 2), "diag_gaussian_600": (4, 4), "ar1_65": (2, 1), "std_normal_1": (1, 1)}.get(name)
+    want_shape = {"ar1_200": (4, 1), "ar1_300": (4, 2), "diag_gaussian_600": (4, 4), "ar1_65": (2, 1), "std_normal_1": (1, 1),
+                  "glm_63_3_bernoulli": (1, 1), "glm_130_130_poisson": (4, 1)}.get(name)
     if want_shape is not None:
         assert res["shape"][1:] == want_shape, res
 
