@@ -14,7 +14,6 @@ from tests import _glm_model as M
 
 TAU, ISIG2 = M.PRIOR_SCALE ** -2, M.SIGMA ** -2
 SEEDS_FROM, CHAIN = 4321, 1          # the diagonal chains: seeds derive_seeds(4321, 2), chain 1 (start: jitter of seeds[0])
-FLOOR = 1e-9                         # tests/_gpu_util.replay_iterations_on_device: an oracle margin below this is a coin flip
 
 
 # ---- the two statements of the posterior -----------------------------------------------------------------------------------
@@ -208,26 +207,19 @@ def device_step(c, target=None, **kw):
 
 @functools.lru_cache(maxsize=None)
 def oracle_chain(c):
-    """(snaps, outs) of case ``c``'s oracle chain (tests/_gpu_util.oracle_chain_snapshots / dense_snapshots), computed once
-    per process and shared by every variant that replays it; nothing in it is modified afterwards."""
-    from tests import _gpu_util as U
+    """(snaps, outs) of case ``c``'s oracle chain (tests/_replay.record_chain), computed once per process and shared by every
+    variant that replays it; nothing in it is modified afterwards."""
+    from tests._replay import record_chain
 
     ostep, start, seed = oracle_step(c)
-    run = U.dense_snapshots if c.kind in DENSE else U.oracle_chain_snapshots
-    snaps, outs = run(ostep, start, seed, c.tune, c.draws)
+    snaps, outs = record_chain(ostep, start, np.random.RandomState(int(seed)), c.tune, c.draws)
     for o in outs:
         o["q"].setflags(write=False)
     return snaps, outs
 
 
-def skip_floor(c):
-    """The oracle margin below which the replay of case ``c`` does not compare an iteration."""
-    from tests.test_gpu_dense import DECISION   # (float32-born momentum; the module touches no device at import)
+def rules(c):
+    """What the replay of case ``c`` asserts, the margin and the floor it skips an iteration by included (tests/_replay.Rules)."""
+    from tests._replay import Rules, dense_rules
 
-    return DECISION if c.kind in F32_BORN else FLOOR
-
-
-def oracle_margin(c, out):
-    """The margin the replay of case ``c`` skips an iteration by: replay_dense's ``margin`` (the smallest of the three) for
-    the dense kinds, the smaller of ``margin`` and ``turn_margin`` for replay_iterations_on_device."""
-    return out["margin"] if c.kind in DENSE else min(out["margin"], out["turn_margin"])
+    return dense_rules(c.kind in F32_BORN) if c.kind in DENSE else Rules.diag()

@@ -145,106 +145,6 @@ def assert_chain_matches(got_q, got_stats, want_q, want_stats, margins, label=""
 
 
 # ---------------------------------------------------------------------------------------------------
-# per-iteration ("teacher-forced") parity: every iteration of an oracle chain is replayed on the device
-# from the oracle's exact pre-iteration state, all iterations of a chain at once (one per wavefront).
-# ---------------------------------------------------------------------------------------------------
-def oracle_chain_snapshots(ostep, start, seed, tune, draws):
-    """Run one oracle chain like sampling.py:481-521; return (snapshots, outputs) per iteration."""
-    from oracle import lmc_oracle as orc  # noqa: F401
-
-    rng = np.random.RandomState(int(seed))
-    q = np.array(start, dtype="d")
-    ostep.tune = bool(tune)
-    ostep.reset_tuning()
-    snaps, outs = [], []
-    adaptive = hasattr(ostep.pot, "fore")
-    for i in range(tune + draws):
-        if i == 0:
-            ostep.iter_count = 0
-        if i == tune:
-            ostep.tune = False
-        pot, ad = ostep.pot, ostep.adapt
-        snap = dict(q=q.copy(), rng=rng.get_state(), tune=ostep.tune, iter_count=ostep.iter_count,
-                    var=pot.var.copy(), log_step=float(np.ravel(ad.log_step)[0]), log_bar=float(np.ravel(ad.log_bar)[0]),
-                    hbar=float(np.ravel(ad.hbar)[0]), da_count=ad.count, n_samples=pot.n_samples)
-        if adaptive:
-            snap.update(fore_mean=pot.fore.mean.copy(), fore_raw_var=pot.fore.raw_var.copy(), fore_w_sum=pot.fore.w_sum,
-                        back_mean=pot.back.mean.copy(), back_raw_var=pot.back.raw_var.copy(), back_w_sum=pot.back.w_sum,
-                        window=pot.window)
-        q, st = ostep.astep(q, rng)
-        snaps.append(snap)
-        outs.append(dict(q=q.copy(), stats={k: np.ravel(v)[0] for k, v in st.items()}, margin=ostep.last_margins.lb,
-                         turn_margin=ostep.last_margins.turn, rng_pos=rng.get_state()[2]))
-    return snaps, outs
-
-
-def replay_iterations_on_device(step, snaps, outs, label="", expect_plan=None):
-    """One engine, one wavefront per snapshot; run ONE iteration everywhere; compare with the oracle.
-    ``expect_plan``: the LDS plan ("shallow" / "deep") the launch must have run under (Engine.last_run_plan()).
-    Returns (n_checked, n_fragile)."""
-    from littlemcmc_amd import _abi
-
-    checked = fragile = 0
-    for tune_flag in (True, False):
-        idx = [i for i, s in enumerate(snaps) if s["tune"] == tune_flag]
-        if not idx:
-            continue
-        n = len(idx)
-        eng = step._make_engine(n)
-        try:
-            eng.set_position(np.stack([snaps[i]["q"] for i in idx]))
-            for c, i in enumerate(idx):
-                eng.set_rng_state(c, snaps[i]["rng"])
-            state = {k: np.stack([np.asarray(snaps[i][k]) for i in idx]) for k in
-                     ("var", "log_step", "log_bar", "hbar", "da_count", "iter_count", "n_samples")}
-            if "fore_mean" in snaps[idx[0]]:
-                for k in ("fore_mean", "fore_raw_var", "back_mean", "back_raw_var", "fore_w_sum", "back_w_sum", "window"):
-                    state[k] = np.stack([np.asarray(snaps[i][k]) for i in idx])
-            if eng.mass_f64:   # QuadPotentialDiagAdapt(dtype="float64"): the diagonal travels in its own dtype
-                state["var64"] = state.pop("var")
-            eng.set_chain_state(state)
-            eng.reserve(1, keep_trace=True)
-            eng.run(1 if tune_flag else 0, 0, 1)
-            assert not eng.status().any()
-            if expect_plan is not None:
-                assert eng.last_run_plan() == expect_plan, (label, eng.last_run_plan(), eng.kernel_shape())
-            q = eng.trace()[:, 0]
-            stats = {k: v[:, 0] for k, v in step._stats_from_engine(eng, 0, 1).items()}
-            after = eng.get_chain_state()
-            for c, i in enumerate(idx):
-                want = outs[i]
-                tag = "%s iter %d" % (label, i)
-                if want["margin"] < 1e-9 or want["turn_margin"] < 1e-9:   # a coin flip within reduction-order noise
-                    fragile += 1
-                    continue
-                for name, val in want["stats"].items():
-                    got = stats[name][c]
-                    if name in INT_STATS:
-                        assert got == val, (tag, name, got, val)
-                    else:
-                        assert np.isclose(got, val, rtol=1e-10, atol=1e-10), (tag, name, got, val)
-                np.testing.assert_allclose(q[c], want["q"], rtol=1e-11, atol=1e-12, err_msg=tag)
-                assert eng.get_rng_state(c)[2] == want["rng_pos"], tag
-                if i + 1 < len(snaps):   # adaptation state after the iteration == oracle's next snapshot
-                    nxt = snaps[i + 1]
-                    np.testing.assert_allclose(after["var"][c], nxt["var"], rtol=2e-7, err_msg=tag + " var")
-                    if eng.mass_f64:
-                        np.testing.assert_allclose(after["var64"][c], nxt["var"], rtol=1e-12, err_msg=tag + " var64")
-                    for k in ("log_step", "log_bar", "hbar"):
-                        assert np.isclose(after[k][c], nxt[k], rtol=1e-11, atol=1e-13), (tag, k, after[k][c], nxt[k])
-                    assert after["da_count"][c] == nxt["da_count"] and after["n_samples"][c] == nxt["n_samples"], tag
-                    if "fore_mean" in nxt and nxt["tune"] == tune_flag:
-                        for k in ("fore_mean", "fore_raw_var", "back_mean", "back_raw_var"):
-                            np.testing.assert_allclose(after[k][c], nxt[k], rtol=1e-11, atol=1e-13, err_msg=tag + " " + k)
-                        assert after["fore_w_sum"][c] == nxt["fore_w_sum"] and after["back_w_sum"][c] == nxt["back_w_sum"], tag
-                        assert after["window"][c] == nxt["window"], (tag, after["window"][c], nxt["window"])
-                checked += 1
-        finally:
-            eng.close()
-    return checked, fragile
-
-
-# ---------------------------------------------------------------------------------------------------
 # oracle chains inside a full-size job: the seeds are prefix stable over the GLOBAL chain index space, so chain i of
 # a 65 536-chain device job is the oracle's one-chain run with seeds[i] (SURVEY.md section 8d)
 # ---------------------------------------------------------------------------------------------------
@@ -279,6 +179,7 @@ def replay_golden_run(golden_dir, name, lds_plan="auto"):
 
     from oracle import lmc_oracle as orc
     from oracle import targets as OT
+    from tests._replay import Rules, assert_replay, record_chain, run_snapshots
 
     g = np.load(os.path.join(golden_dir, name + ".npz"))
     d, chains, tune, draws = int(g["d"]), int(g["chains"]), int(g["tune"]), int(g["draws"])
@@ -301,117 +202,16 @@ def replay_golden_run(golden_dir, name, lds_plan="auto"):
             _s2, step = lmc.init_nuts(tgt, d, random_seed=seeds, **dkw)
             np.testing.assert_array_equal(_s, _s2)
             np.testing.assert_array_equal(_s, start)
-        snaps, outs = oracle_chain_snapshots(ostep, start, seeds[c], tune, draws)
+        snaps, outs = record_chain(ostep, start, np.random.RandomState(seeds[c]), tune, draws)
         # the oracle chain IS the golden chain on the capture host; elsewhere (other BLAS) allow drift
         same = np.allclose(np.array([o["q"] for o in outs]), g["trace"][c], rtol=1e-9, atol=1e-12)
-        checked, fragile = replay_iterations_on_device(step, snaps, outs, label="%s chain %d" % (name, c),
-                                                       expect_plan=None if lds_plan == "auto" else lds_plan)
-        total_checked += checked
-        total_fragile += fragile
+        ran = run_snapshots(step, snaps)
+        if lds_plan != "auto":
+            assert ran.kernels("plan") == {lds_plan}, (name, c, ran.engines)
+        res = assert_replay(ran, snaps, outs, Rules.diag(), "%s chain %d" % (name, c))
+        total_checked += res.checked
+        total_fragile += res.skipped
         if same:
             np.testing.assert_array_equal(np.array([o["stats"]["diverging"] for o in outs]),
                                           g["stat_diverging"][c, :, 0])
     return total_checked, total_fragile, chains * (tune + draws)
-
-
-# ---------------------------------------------------------------------------------------------------
-# dense mass matrices: oracle chains generated on the fly, every iteration replayed on the device from the oracle's exact
-# pre-iteration state (tests/test_gpu_dense.py, tests/test_gpu_dense_shapes.py)
-# ---------------------------------------------------------------------------------------------------
-def dense_snapshots(ostep, start, seed, tune, draws):
-    """Run one oracle chain; per iteration the pre-iteration state (snapshot) and what the oracle computed from it."""
-    from oracle import lmc_oracle as orc
-
-    rng = np.random.RandomState(int(seed))
-    q = np.array(start, dtype="d")
-    ostep.tune = bool(tune)
-    ostep.reset_tuning()
-    snaps, outs = [], []
-    for i in range(tune + draws):
-        if i == 0:
-            ostep.iter_count = 0
-        if i == tune:
-            ostep.tune = False
-        pot, ad = ostep.pot, ostep.adapt
-        snap = dict(q=q.copy(), rng=rng.get_state(), tune=ostep.tune, iter_count=ostep.iter_count,
-                    log_step=float(np.ravel(ad.log_step)[0]), log_bar=float(np.ravel(ad.log_bar)[0]),
-                    hbar=float(np.ravel(ad.hbar)[0]), da_count=ad.count, n_samples=pot.n_samples)
-        if isinstance(pot, orc.FullAdaptPotential):
-            snap.update(cov=pot.cov.copy(), chol=pot.chol.copy(), fore_mean=pot.fore.mean.copy(),
-                        fore_raw_cov=pot.fore.raw.copy(), fore_n=pot.fore.n_samples, back_mean=pot.back.mean.copy(),
-                        back_raw_cov=pot.back.raw.copy(), back_n=pot.back.n_samples, window=pot.window,
-                        previous_update=pot.previous_update)
-        q, st = ostep.astep(q, rng)
-        m = ostep.last_margins
-        snaps.append(snap)
-        outs.append(dict(q=q.copy(), stats={k: np.ravel(v)[0] for k, v in st.items()},
-                         margin=min(m.lb, m.turn, m.div), rng_pos=rng.get_state()[2]))
-    return snaps, outs
-
-
-def replay_dense(dstep, snaps, outs, tol, floor, label, expect_kernel=None, skip=None):
-    """Replay every snapshot for ONE iteration on the device (one chain per snapshot; tuning and sampling iterations in
-    two engines) and compare with the oracle: integer statistics and the generator's position exact, positions, float
-    statistics and the dual-averaging state to ``tol`` relative. An iteration whose oracle decision margin is below
-    ``floor``, or for which ``skip(i)`` names a reason, is not compared. ``expect_kernel``: the dense kernel every launch
-    must have run (Engine.last_run_dense_kernel()).
-    Returns dict(checked, skipped, worst_q, worst_stat): the largest position / float statistic error seen, in units of tol."""
-    res = dict(checked=0, skipped=0, worst_q=0.0, worst_stat=0.0)
-    for tune_flag in (True, False):
-        idx = [i for i, s in enumerate(snaps) if s["tune"] == tune_flag]
-        if not idx:
-            continue
-        eng = dstep._make_engine(len(idx))
-        try:
-            eng.set_position(np.stack([snaps[i]["q"] for i in idx]))
-            for c, i in enumerate(idx):
-                eng.set_rng_state(c, snaps[i]["rng"])
-            eng.set_chain_state({k: np.stack([np.asarray(snaps[i][k]) for i in idx]) for k in
-                                 ("log_step", "log_bar", "hbar", "da_count", "iter_count", "n_samples")})
-            if "cov" in snaps[idx[0]]:
-                eng.set_dense_state({k: np.stack([np.asarray(snaps[i][k]) for i in idx]) for k in
-                                     ("cov", "chol", "fore_mean", "fore_raw_cov", "fore_n", "back_mean", "back_raw_cov",
-                                      "back_n", "window", "previous_update")})
-            eng.reserve(1, keep_trace=True)
-            eng.run(1 if tune_flag else 0, 0, 1)
-            assert not eng.status().any()
-            if expect_kernel is not None:
-                assert eng.last_run_dense_kernel() == expect_kernel, (label, eng.last_run_dense_kernel(), expect_kernel)
-            q = eng.trace()[:, 0]
-            stats = {k: v[:, 0] for k, v in dstep._stats_from_engine(eng, 0, 1).items()}
-            after = eng.get_chain_state()
-            dense_after = eng.get_dense_state(fields=("cov",)) if "cov" in snaps[idx[0]] else None
-            for c, i in enumerate(idx):
-                want, tag = outs[i], "%s iter %d" % (label, i)
-                if want["margin"] < floor or (skip is not None and skip(i)):
-                    res["skipped"] += 1
-                    continue
-                escale = 1 + abs(want["stats"].get("energy", 0.0))
-                for sname, val in want["stats"].items():
-                    got = stats[sname][c]
-                    if sname in INT_STATS:
-                        assert got == val, (tag, sname, got, val, want["margin"])
-                    else:
-                        assert np.isclose(got, val, rtol=tol, atol=tol * escale), (tag, sname, got, val)
-                        if np.isfinite(val):
-                            res["worst_stat"] = max(res["worst_stat"], abs(got - val) / (tol * (abs(val) + escale)))
-                qs = 1 + np.abs(want["q"]).max()
-                np.testing.assert_allclose(q[c], want["q"], rtol=tol, atol=tol * qs, err_msg=tag)
-                res["worst_q"] = max(res["worst_q"], float(np.max(np.abs(q[c] - want["q"]) / (tol * (np.abs(want["q"]) + qs)))))
-                assert eng.get_rng_state(c)[2] == want["rng_pos"], tag
-                if i + 1 < len(snaps):   # dual averaging after the iteration == the oracle's next snapshot
-                    nxt = snaps[i + 1]
-                    # the accept statistic is compared at tol * escale (a float32-born start energy moves it by a few
-                    # float32 ulps of the kinetic energy); hbar averages it and log_step = mu - sqrt(t) / gamma * hbar
-                    # (step_sizes.py, gamma = 0.05) carries it with that gain
-                    da_tol = tol * escale * (1.0 + np.sqrt(max(float(nxt["da_count"]), 1.0)) / 0.05)
-                    for k in ("log_step", "log_bar", "hbar"):
-                        assert np.isclose(after[k][c], nxt[k], rtol=tol, atol=da_tol), (tag, k, after[k][c], nxt[k])
-                    assert after["da_count"][c] == nxt["da_count"] and after["n_samples"][c] == nxt["n_samples"], tag
-                    if dense_after is not None and nxt["tune"] == tune_flag:
-                        cs = np.abs(nxt["cov"]).max()
-                        np.testing.assert_allclose(dense_after["cov"][c], nxt["cov"], rtol=0, atol=2 * tol * cs, err_msg=tag)
-                res["checked"] += 1
-        finally:
-            eng.close()
-    return res

@@ -2,7 +2,7 @@
 
 Every iteration of every oracle chain of tests/_glm_oracle.CASES is replayed, from a deep copy of the step and the generator,
 with a second and independent statement of the posterior (np.longdouble, BLAS order: _glm_oracle.oracle_glm_longdouble), and
-compared as tests/_gpu_util.replay_iterations_on_device compares a device iteration with the oracle's: integer statistics
+compared by the comparison the device replay runs (tests/_replay.iteration_errors under Rules.diag()): integer statistics
 equal, positions at rtol 1e-11 / atol 1e-12, float statistics at 1e-10. These are the tightest comparisons any case is held
 to on the device (the dense float64 cases allow atol 1e-11 (1 + max |q|), the float32-born ones 1e-5), so one table serves all.
 
@@ -16,7 +16,7 @@ import numpy as np
 import pytest
 
 from tests import _glm_oracle as GO
-from tests._gpu_util import INT_STATS
+from tests._replay import Rules, chain_iterations, iteration_errors
 
 CPU_ITERATIONS_WIDE = 12      # the oracle costs ~50 ms per iteration for d >= 257: a prefix of those chains is replayed here
 _table = []
@@ -31,37 +31,23 @@ def _separation_table():
         print("%-28s %5d %11.4f %8d %8d %5d" % row)
 
 
-def _same(got_q, got_stats, want_q, want_stats):
-    """replay_iterations_on_device's comparisons of one iteration: (all hold, position error in units of the tolerance)."""
-    ok = True
-    for name, val in want_stats.items():
-        got = got_stats[name]
-        ok &= bool(got == val) if name in INT_STATS else bool(np.isclose(got, val, rtol=1e-10, atol=1e-10))
-    ok &= bool(np.allclose(got_q, want_q, rtol=1e-11, atol=1e-12))
-    return ok, float(np.max(np.abs(got_q - want_q) / (1e-12 + 1e-11 * np.abs(want_q))))
-
-
 def _replay_with(c, f_other, n_iter):
-    """The oracle chain of case ``c`` (the loop of tests/_gpu_util.oracle_chain_snapshots); before every iteration the step
-    and the generator are deep-copied, the copy is given ``f_other`` and takes the iteration too.
+    """The oracle chain of case ``c`` (record_chain's driver: tests/_replay.chain_iterations); before every iteration the step
+    and the generator are deep-copied, the copy is given ``f_other`` and takes the iteration too: the twin's iteration is
+    "got", the oracle's "want", under Rules.diag() with no next snapshot (iteration_errors).
     Returns [(all comparisons hold, separation)] per iteration and the chain's positions."""
     ostep, start, seed = GO.oracle_step(c)
     rng = np.random.RandomState(int(seed))
     q = np.array(start, dtype="d")
-    ostep.tune = bool(c.tune)
-    ostep.reset_tuning()
     out, qs = [], []
-    for i in range(n_iter):
-        if i == 0:
-            ostep.iter_count = 0
-        if i == c.tune:
-            ostep.tune = False
+    for _i in chain_iterations(ostep, c.tune, n_iter):
         twin, twin_rng = copy.deepcopy(ostep), copy.deepcopy(rng)
         twin.f = f_other
         tq, tst = twin.astep(q.copy(), twin_rng)
         q, st = ostep.astep(q, rng)
-        stats = {k: np.ravel(v)[0] for k, v in st.items()}
-        out.append(_same(tq, {k: np.ravel(v)[0] for k, v in tst.items()}, q, stats))
+        errors, separation, _stat = iteration_errors(dict(q=tq, stats={k: np.ravel(v)[0] for k, v in tst.items()}),
+                                                     dict(q=q, stats={k: np.ravel(v)[0] for k, v in st.items()}), None, Rules.diag())
+        out.append((not errors, separation))
         qs.append(q.copy())
     return out, np.array(qs)
 
@@ -79,12 +65,12 @@ def test_two_statements_of_the_posterior_replay_each_other(c):
     # the chain replayed here IS the chain the device test replays
     np.testing.assert_array_equal(qs, np.array([o["q"] for o in outs[:n]]))
     worst = max(sep for _ok, sep in res)
-    low = sum(GO.oracle_margin(c, o) < GO.skip_floor(c) for o in outs)
+    low = sum(GO.rules(c).skips(o) for o in outs)
     sizes = [o["stats"].get("tree_size", o["stats"].get("n_steps")) for o in outs]
     div = sum(bool(o["stats"]["diverging"]) for o in outs)
     _table.append((GO.case_id(c), n, worst, low, int(max(sizes)), div))
     print("%s: %d iterations, separation %.4f of the tolerance, %d margins below %g, largest tree %d, %d divergences" % (
-        GO.case_id(c), n, worst, low, GO.skip_floor(c), max(sizes), div))
+        GO.case_id(c), n, worst, low, GO.rules(c).floor, max(sizes), div))
     assert all(ok for ok, _sep in res), [i for i, (ok, _s) in enumerate(res) if not ok]
     assert worst < 1.0 / 50.0, worst
     assert low <= 2, low

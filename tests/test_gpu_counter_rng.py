@@ -12,7 +12,8 @@ from oracle import lmc_oracle as orc
 from oracle import targets as OT
 from tests import _counter_model as cm
 from tests import _glm_oracle as GO
-from tests._gpu_util import INT_STATS, device_target
+from tests._gpu_util import device_target
+from tests._replay import DeviceIterations, Rules, assert_replay, chain_state_of, engine_report, record_chain
 
 pytestmark = pytest.mark.gpu
 
@@ -116,29 +117,27 @@ def _steps(family, d, kind, extra, seeds):
     return step, ostep, start
 
 
-def _oracle_chain(ostep, start, rng, n_tune, n_it):
-    """tests/_gpu_util.oracle_chain_snapshots on an explicit rng object (no rng.get_state())."""
-    q = np.array(start, dtype="d")
-    ostep.tune = n_tune > 0
-    ostep.reset_tuning()
-    ostep.iter_count = 0
-    snaps, outs = [], []
-    for i in range(n_it):
-        if i == n_tune:
-            ostep.tune = False
-        pot, ad = ostep.pot, ostep.adapt
-        snap = dict(q=q.copy(), tune=ostep.tune, iter_count=ostep.iter_count, var=pot.var.copy(),
-                    log_step=float(np.ravel(ad.log_step)[0]), log_bar=float(np.ravel(ad.log_bar)[0]),
-                    hbar=float(np.ravel(ad.hbar)[0]), da_count=ad.count, n_samples=getattr(pot, "n_samples", 0))
-        if hasattr(pot, "fore"):
-            snap.update(fore_mean=pot.fore.mean.copy(), fore_raw_var=pot.fore.raw_var.copy(), fore_w_sum=pot.fore.w_sum,
-                        back_mean=pot.back.mean.copy(), back_raw_var=pot.back.raw_var.copy(), back_w_sum=pot.back.w_sum,
-                        window=pot.window)
-        q, st = ostep.astep(q, rng)
-        snaps.append(snap)
-        outs.append(dict(q=q.copy(), stats={k: np.ravel(v)[0] for k, v in st.items()}, margin=ostep.last_margins.lb,
-                         turn_margin=ostep.last_margins.turn))
-    return snaps, outs
+def _run_chains(step, eng, chain_snaps, n_tune):
+    """The device half in the counter layout (tests/_replay.run_snapshots is the MT19937 one): the stream is keyed by (seed,
+    iteration), so the K seeded chains of ``eng`` take iteration t of every chain in one launch, eng.run(n_tune, t, 1).
+    Returns one DeviceIterations per chain; compares nothing."""
+    n_it = len(chain_snaps[0])
+    ran = [DeviceIterations(n_it) for _ in chain_snaps]
+    eng.reserve(n_it, keep_trace=True)
+    for t in range(n_it):
+        now = [snaps[t] for snaps in chain_snaps]
+        eng.set_position(np.stack([s["q"] for s in now]))
+        eng.set_chain_state(chain_state_of(now, eng.mass_f64))
+        eng.run(n_tune, t, 1)
+        assert not eng.status().any()
+        q = eng.trace(t, 1)[:, 0]
+        stats = {k: v[:, 0] for k, v in step._stats_from_engine(eng, t, 1).items()}
+        after = eng.get_chain_state()
+        for c, s in enumerate(now):
+            ran[c].put(t, c, s["tune"], q, stats, after)
+    for r in ran:
+        r.engines.append(engine_report(eng))
+    return ran
 
 
 def _replay(name):
@@ -149,56 +148,17 @@ def _replay(name):
     seeds = lmc.distributed.global_seeds(SEED, K)
     step, make_ostep, start = _steps(family, d, kind, extra, seeds)
     eng = step._make_engine(K)
-    checked = fragile = 0
     try:
         eng.seed(seeds)                      # once: the streams are keyed by these seeds and nothing else
         rng_before = [eng.get_rng_state(c) for c in range(K)]
         normals = np.stack([eng.counter_draws(t)[0] for t in range(n_it)])      # [T, K, d]: the device's own normals
-        chains = []
-        used = []
+        chains, used = [], []
         for c in range(K):
             rng = cm.CounterRng(seeds[c], normals[:, c])
-            chains.append(_oracle_chain(make_ostep(), start, rng, n_tune, n_it))
+            chains.append(record_chain(make_ostep(), start, rng, n_tune, n_it - n_tune))
             used.append(rng.finish())
         used = np.array(used)                # [K, T] uniforms the oracle consumed
-        eng.reserve(n_it, keep_trace=True)
-        keys = ["var", "log_step", "log_bar", "hbar", "da_count", "iter_count", "n_samples"]
-        if "fore_mean" in chains[0][0][0]:
-            keys += ["fore_mean", "fore_raw_var", "back_mean", "back_raw_var", "fore_w_sum", "back_w_sum", "window"]
-        for t in range(n_it):
-            eng.set_position(np.stack([chains[c][0][t]["q"] for c in range(K)]))
-            eng.set_chain_state({k: np.stack([np.asarray(chains[c][0][t][k]) for c in range(K)]) for k in keys})
-            eng.run(n_tune, t, 1)
-            assert not eng.status().any()
-            q = eng.trace(t, 1)[:, 0]
-            stats = {k: v[:, 0] for k, v in step._stats_from_engine(eng, t, 1).items()}
-            after = eng.get_chain_state()
-            for c in range(K):
-                snaps, outs = chains[c]
-                want = outs[t]
-                tag = "%s chain %d iter %d" % (name, c, t)
-                if want["margin"] < 1e-9 or want["turn_margin"] < 1e-9:   # a coin flip within reduction-order noise
-                    fragile += 1
-                    continue
-                for sname, val in want["stats"].items():
-                    got = stats[sname][c]
-                    if sname in INT_STATS:
-                        assert got == val, (tag, sname, got, val)
-                    else:
-                        assert np.isclose(got, val, rtol=1e-10, atol=1e-10), (tag, sname, got, val)
-                np.testing.assert_allclose(q[c], want["q"], rtol=1e-11, atol=1e-12, err_msg=tag)
-                if t + 1 < n_it:   # adaptation state after the iteration == the oracle's next snapshot
-                    nxt = snaps[t + 1]
-                    np.testing.assert_allclose(after["var"][c], nxt["var"], rtol=2e-7, err_msg=tag + " var")
-                    for k in ("log_step", "log_bar", "hbar"):
-                        assert np.isclose(after[k][c], nxt[k], rtol=1e-11, atol=1e-13), (tag, k, after[k][c], nxt[k])
-                    assert after["da_count"][c] == nxt["da_count"] and after["n_samples"][c] == nxt["n_samples"], tag
-                    if "fore_mean" in nxt and nxt["tune"] == snaps[t]["tune"]:
-                        for k in ("fore_mean", "fore_raw_var", "back_mean", "back_raw_var"):
-                            np.testing.assert_allclose(after[k][c], nxt[k], rtol=1e-11, atol=1e-13, err_msg=tag + " " + k)
-                        assert after["fore_w_sum"][c] == nxt["fore_w_sum"] and after["back_w_sum"][c] == nxt["back_w_sum"], tag
-                        assert after["window"][c] == nxt["window"], (tag, after["window"][c], nxt["window"])
-                checked += 1
+        ran = _run_chains(step, eng, [snaps for snaps, _outs in chains], n_tune)
         # the chains' MT19937 state was never touched
         for c in range(K):
             now = eng.get_rng_state(c)
@@ -207,7 +167,9 @@ def _replay(name):
         shape, lds = eng.kernel_shape(), eng.run_lds_bytes()
     finally:
         eng.close()
-    res = dict(checked=checked, fragile=fragile, total=K * n_it, max_used=int(used.max()), over128=int((used > 128).sum()),
+    done = [assert_replay(ran[c], snaps, outs, Rules.diag(), "%s chain %d" % (name, c))
+            for c, (snaps, outs) in enumerate(chains)]
+    res = dict(checked=sum(r.checked for r in done), fragile=sum(r.skipped for r in done), total=K * n_it, max_used=int(used.max()), over128=int((used > 128).sum()),
                over256=int((used > 256).sum()), shape=shape, lds=lds)
     print("%s: %s" % (name, res))
     _REPLAYED[name] = res

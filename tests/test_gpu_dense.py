@@ -5,7 +5,7 @@ Tolerances. Everything downstream of a float64 matrix sweep agrees with numpy's 
 (rtol 1e-9 here). Two quantities are float32 in the reference and are NOT reproducible bit for bit: the momentum
 draw ``solve_triangular(chol.T, float32 normals)`` (BLAS strsv, float32 accumulation) and the start state's
 ``sgemv`` velocity / ``sdot`` kinetic energy. They agree to a few float32 ulps times the condition of the solve
-(F32 = 2e-5 relative below); a chain that starts from such a momentum then tracks the reference to REPLAY_F32 over
+(F32 = 2e-5 relative below); a chain that starts from such a momentum then tracks the reference to REPLAY_F32 (tests/_replay.py) over
 one iteration, and decisions are compared only where the oracle's decision margin exceeds DECISION. Observed on
 MI355X over the 1770 captured iterations (tools/dense_parity_report.py): no integer statistic differs anywhere;
 positions agree to 6e-7 (float32-born momentum) / 1e-14 (FullInv), float statistics to 3e-6 / 1e-14 relative.
@@ -19,15 +19,13 @@ import littlemcmc_amd as lmc
 from littlemcmc_amd import _abi
 from oracle import lmc_oracle as orc
 from oracle import targets as otargets
-from tests._gpu_util import INT_STATS, dense_snapshots, device_target, replay_dense
+from tests._gpu_util import device_target
+from tests._replay import REPLAY_F32, assert_replay, dense_rules, record_chain, replay_chain, run_snapshots
 
 pytestmark = pytest.mark.gpu
 
 F32 = 2e-5        # relative agreement of float32-born quantities (momentum solve, start velocity / energy)
 F64 = 1e-9        # everything computed in float64 on both sides
-REPLAY_F32 = 1e-5 # one whole transition started from a float32-born momentum (observed: 6e-7 positions, 3e-6 stats)
-REPLAY_F64 = 1e-11
-DECISION = 1e-4   # smallest oracle decision margin that must reproduce when the momentum is float32-born
 
 
 def _load(golden_dir, name):
@@ -191,74 +189,17 @@ def _oracle_and_device_steps(g):
     return ostep, dstep, start
 
 
-_snapshots = dense_snapshots
-
-
 @pytest.mark.parametrize("name", DENSE_E2E)
 def test_dense_transitions_replay_the_reference_chain(golden_dir, name):
     g = _load(golden_dir, name)
     d, tune, draws = int(g["d"]), int(g["tune"]), int(g["draws"])
     ostep, dstep, start = _oracle_and_device_steps(g)
-    snaps, outs = _snapshots(ostep, start, int(g["seeds"][0]), tune, draws)
+    snaps, outs = record_chain(ostep, start, np.random.RandomState(int(g["seeds"][0])), tune, draws)
     # the oracle chain IS the reference chain (pinned bit for bit by tests/test_oracle_dense_golden.py)
     np.testing.assert_allclose(np.array([o["q"] for o in outs]), g["trace"][0], rtol=1e-9, atol=1e-300)
-    f32_born = str(g["potential"]) not in ("inv", "full64")
-    tol = REPLAY_F32 if f32_born else REPLAY_F64
-    floor = DECISION if f32_born else 1e-9
-    checked = skipped = 0
-    for tune_flag in (True, False):
-        idx = [i for i, s in enumerate(snaps) if s["tune"] == tune_flag]
-        if not idx:
-            continue
-        eng = dstep._make_engine(len(idx))
-        try:
-            eng.set_position(np.stack([snaps[i]["q"] for i in idx]))
-            for c, i in enumerate(idx):
-                eng.set_rng_state(c, snaps[i]["rng"])
-            eng.set_chain_state({k: np.stack([np.asarray(snaps[i][k]) for i in idx]) for k in
-                                 ("log_step", "log_bar", "hbar", "da_count", "iter_count", "n_samples")})
-            adapt = "cov" in snaps[idx[0]]
-            if adapt:
-                eng.set_dense_state({k: np.stack([np.asarray(snaps[i][k]) for i in idx]) for k in
-                                     ("cov", "chol", "fore_mean", "fore_raw_cov", "fore_n", "back_mean", "back_raw_cov",
-                                      "back_n", "window", "previous_update")})
-            eng.reserve(1, keep_trace=True)
-            eng.run(1 if tune_flag else 0, 0, 1)
-            assert not eng.status().any()
-            q = eng.trace()[:, 0]
-            stats = {k: v[:, 0] for k, v in dstep._stats_from_engine(eng, 0, 1).items()}
-            after = eng.get_chain_state()
-            dense_after = eng.get_dense_state() if adapt else None
-            for c, i in enumerate(idx):
-                want, tag = outs[i], "%s iter %d" % (name, i)
-                assert eng.get_rng_state(c)[2] == want["rng_pos"] or want["margin"] < floor, tag
-                if want["margin"] < floor:
-                    skipped += 1
-                    continue
-                for sname, val in want["stats"].items():
-                    got = stats[sname][c]
-                    if sname in INT_STATS:
-                        assert got == val, (tag, sname, got, val, want["margin"])
-                    else:
-                        assert np.isclose(got, val, rtol=tol, atol=tol * (1 + abs(want["stats"].get("energy", 0.0)))), (
-                            tag, sname, got, val)
-                np.testing.assert_allclose(q[c], want["q"], rtol=tol, atol=tol * (1 + np.abs(want["q"]).max()), err_msg=tag)
-                if i + 1 < len(snaps):
-                    nxt = snaps[i + 1]
-                    for k in ("log_step", "log_bar", "hbar"):
-                        assert np.isclose(after[k][c], nxt[k], rtol=tol, atol=tol), (tag, k)
-                    assert after["da_count"][c] == nxt["da_count"] and after["n_samples"][c] == nxt["n_samples"], tag
-                    if adapt and nxt["tune"] == tune_flag:
-                        cs = np.abs(nxt["cov"]).max()
-                        np.testing.assert_allclose(dense_after["cov"][c], nxt["cov"], rtol=0, atol=2 * tol * cs, err_msg=tag)
-                        np.testing.assert_allclose(dense_after["chol"][c], nxt["chol"], rtol=0, atol=10 * tol * np.sqrt(cs), err_msg=tag)
-                        assert dense_after["window"][c] == nxt["window"], tag
-                        assert dense_after["previous_update"][c] == nxt["previous_update"], tag
-                        assert dense_after["fore_n"][c] == nxt["fore_n"] and dense_after["back_n"][c] == nxt["back_n"], tag
-                checked += 1
-        finally:
-            eng.close()
-    assert checked >= 0.97 * (tune + draws), (checked, skipped)
+    rules = dense_rules(str(g["potential"]) not in ("inv", "full64"), da_atol="tol", dense_state="all")
+    res = assert_replay(run_snapshots(dstep, snaps, rules.dense_fields), snaps, outs, rules, name)
+    assert res.checked >= 0.97 * (tune + draws), res
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -300,12 +241,6 @@ def test_dense_adaptation_learns_the_target_covariance():
 # ---------------------------------------------------------------------------------------------------
 # wider vectors (2 and 4 elements per thread, padded lanes): oracle chains generated on the fly
 # ---------------------------------------------------------------------------------------------------
-def _replay(ostep, dstep, start, seed, tune, draws, f32_born, label):
-    snaps, outs = _snapshots(ostep, start, seed, tune, draws)
-    return replay_dense(dstep, snaps, outs, REPLAY_F32 if f32_born else REPLAY_F64, DECISION if f32_born else 1e-9,
-                        label)["checked"]
-
-
 @pytest.mark.parametrize("d,family", [(100, "ar1"), (130, "std_normal"), (200, "ar1"), (256, "std_normal")])
 def test_dense_adapt_wide_vectors(d, family):
     of = otargets.make(family, d)
@@ -315,7 +250,8 @@ def test_dense_adapt_wide_vectors(d, family):
     start_d, dstep = lmc.init_nuts(tgt, d, init="jitter+adapt_full", random_seed=[seed])
     np.testing.assert_array_equal(start, start_d)
     tune, draws = 14, 4
-    assert _replay(ostep, dstep, start, seed, tune, draws, True, "adapt_full d=%d" % d) >= tune + draws - 2
+    res = replay_chain(ostep, dstep, start, seed, tune, draws, dense_rules(True), "adapt_full d=%d" % d)
+    assert res.checked >= tune + draws - 2
 
 
 @pytest.mark.parametrize("d,kind", [(130, "full"), (200, "inv"), (256, "full")])
@@ -328,8 +264,8 @@ def test_dense_fixed_wide_vectors(d, kind):
     ostep = orc.Step(of, d, kind="nuts", potential=orc.quad_potential(mat, kind == "full"))
     dstep = lmc.NUTS(tgt, d, potential=_pot(kind, mat))
     start = 0.1 * rs.randn(d)
-    n = _replay(ostep, dstep, start, 4242 + d, 10, 4, kind == "full", "%s d=%d" % (kind, d))
-    assert n >= 12
+    res = replay_chain(ostep, dstep, start, 4242 + d, 10, 4, dense_rules(kind == "full"), "%s d=%d" % (kind, d))
+    assert res.checked >= 12
 
 
 def test_full_adapt_two_chains_are_independent_not_carried_over(golden_dir):

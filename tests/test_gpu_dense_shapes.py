@@ -25,8 +25,8 @@ from littlemcmc_amd import _abi
 from littlemcmc_amd._blas_probe import emulate_sdot
 from oracle import lmc_oracle as orc
 from oracle import targets as otargets
-from tests._gpu_util import INT_STATS, dense_snapshots, replay_dense
-from tests.test_gpu_dense import DECISION, REPLAY_F32, REPLAY_F64
+from tests._gpu_util import INT_STATS
+from tests._replay import DECISION, REPLAY_F32, Rules, assert_replay, dense_rules, record_chain, run_snapshots
 
 pytestmark = pytest.mark.gpu
 
@@ -66,14 +66,13 @@ def _steps(d, kind, pot_kind, mat):
 def _sweep(d, kind, pot_kind, mat, expect, seed, label):
     ostep, dstep = _steps(d, kind, pot_kind, mat)
     start = 0.5 * np.random.RandomState(seed).randn(d)
-    snaps, outs = dense_snapshots(ostep, start, seed, TUNE, DRAWS)
-    f32_born = pot_kind == "full"
-    res = replay_dense(dstep, snaps, outs, REPLAY_F32 if f32_born else REPLAY_F64, DECISION if f32_born else 1e-9,
-                       label, expect_kernel=expect)
+    snaps, outs = record_chain(ostep, start, np.random.RandomState(seed), TUNE, DRAWS)
+    ran = run_snapshots(dstep, snaps)
+    assert ran.kernels("dense") == {expect}, (label, ran.engines)
+    res = assert_replay(ran, snaps, outs, dense_rules(pot_kind == "full"), label)
     print("%s: checked %d skipped %d of %d; worst position %.3g / stat %.3g of the tolerance" % (
-        label, res["checked"], res["skipped"], TUNE + DRAWS, res["worst_q"], res["worst_stat"]))
-    assert res["checked"] >= TUNE + DRAWS - 2, res
-    return res
+        label, res.checked, res.skipped, TUNE + DRAWS, res.worst_q, res.worst_stat))
+    assert res.checked >= TUNE + DRAWS - 2, res
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -194,15 +193,16 @@ def test_shared_matrix_kernel_meets_its_float64_contract(d, monkeypatch):
     monkeypatch.setattr(orc, "START_SDOT", _sdot_of(mode))
     ostep = orc.Step(otargets.make("ar1", d), d, kind="nuts", potential=pot)
     start = 0.5 * np.random.RandomState(seed).randn(d)
-    snaps, outs = dense_snapshots(ostep, start, seed, TUNE, DRAWS)
+    snaps, outs = record_chain(ostep, start, np.random.RandomState(seed), TUNE, DRAWS)
     assert len(pot.fragile) == TUNE + DRAWS
-    res = replay_dense(dstep, snaps, outs, CONTRACT, 1e-9, "contract d=%d" % d, expect_kernel="shared",
-                       skip=lambda i: pot.fragile[i])
+    ran = run_snapshots(dstep, snaps)
+    assert ran.kernels("dense") == {"shared"}, ran.engines
+    res = assert_replay(ran, snaps, outs, Rules.dense(CONTRACT, 1e-9), "contract d=%d" % d, skip=lambda i: pot.fragile[i])
     print("contract d=%d: checked %d skipped %d (float32 boundary %d) of %d; worst position %.3g / stat %.3g of %g" % (
-        d, res["checked"], res["skipped"], sum(pot.fragile), TUNE + DRAWS, res["worst_q"], res["worst_stat"], CONTRACT))
+        d, res.checked, res.skipped, sum(pot.fragile), TUNE + DRAWS, res.worst_q, res.worst_stat, CONTRACT))
     # skips: oracle margins below 1e-9, and momentum / start-velocity elements within the (rigorous, so generous) float64
     # error bound of a float32 rounding boundary -- 0 to 3 of 19 per shape
-    assert res["checked"] >= TUNE + DRAWS - 4, res
+    assert res.checked >= TUNE + DRAWS - 4, res
 
 
 # ---------------------------------------------------------------------------------------------------

@@ -6,12 +6,8 @@ LDS plans, leaf pairs and quads, the transition inlined by kInlineTransition), t
 run_wide_kernel<1|2|4|8, 1> (256 < d <= 512, and every float64 mass diagonal), the dense kernels run_dense_kernel /
 run_dense_coop_kernel, and the HMC transition. Here every iteration of an oracle chain on the float64 statement of the
 posterior (tests/_glm_oracle.py over tests/_glm_model.logp_grad) is replayed on the device from the oracle's exact
-pre-iteration state, with the helpers and tolerances every other family is replayed with (tests/_gpu_util.py):
-
-    diagonal mass      replay_iterations_on_device: integer statistics and the generator's position equal, positions at
-                       rtol 1e-11 / atol 1e-12, float statistics at 1e-10, the adaptation state against the next snapshot
-    dense mass         dense_snapshots + replay_dense at REPLAY_F32 / DECISION where the momentum is float32-born
-                       (QuadPotentialFull, adapt_full) and at REPLAY_F64 / 1e-9 otherwise (tests/test_gpu_dense.py)
+pre-iteration state, with the harness and the rules every other family is replayed with (tests/_replay.py: Rules.diag() for
+the diagonal masses, dense_rules for the dense ones; _glm_oracle.rules).
 
 tests/test_glm_replay_cpu.py shows, without a device, that two independent statements of the posterior stay 500 times below
 these tolerances, that three small errors fail them, and that no chain has more than two iterations under the skip floor.
@@ -23,75 +19,24 @@ import pytest
 
 from tests import _glm_model as M
 from tests import _glm_oracle as GO
-from tests._gpu_util import replay_dense, replay_iterations_on_device
-from tests.test_gpu_dense import DECISION, REPLAY_F32, REPLAY_F64
+from tests._replay import assert_replay, run_snapshots
 
 pytestmark = pytest.mark.gpu
 
 
-class _Ran:
-    """What the engines of a replay ran: ``step._make_engine`` is wrapped so that every engine it makes reports, when the
-    helper closes it, its kernel (plan, leaf group, general kernels, dense kernel, shape) and the iteration it computed.
-    The helpers' signatures stay as they are."""
-
-    def __init__(self, step):
-        self.step, self.engines = step, []
-        make = step._make_engine
-
-        def make_and_watch(*a, **kw):
-            eng = make(*a, **kw)
-            close = eng.close
-
-            def report_and_close():
-                live = getattr(eng, "_h", None) and eng._h.value
-                try:
-                    if live:      # (the helpers close an engine once, after its one launch)
-                        self.engines.append(dict(
-                            plan=eng.last_run_plan(), leaf=eng.last_run_leaf_group(), wide=eng.wide, kind=eng.kind,
-                            dense=eng.last_run_dense_kernel(), shape=eng.kernel_shape(), mass_f64=eng.mass_f64,
-                            q=eng.trace()[:, 0].copy(),
-                            stats={k: v[:, 0].copy() for k, v in step._stats_from_engine(eng, 0, 1).items()}))
-                finally:
-                    close()
-
-            eng.close = report_and_close
-            return eng
-
-        step._make_engine = make_and_watch
-
-    def q(self):
-        """Device positions per iteration, in the chain's order (the helpers run the tuning iterations, then the draws)."""
-        return np.concatenate([e["q"] for e in self.engines])
-
-    def stat(self, name):
-        return np.concatenate([e["stats"][name] for e in self.engines])
-
-    def kernels(self, key):
-        return {e[key] for e in self.engines}
-
-
-def _diag_replay(c, label, expect_plan=None, **step_kw):
-    """replay_iterations_on_device on the memoised oracle chain of ``c``; prints checked / skipped and the worst position
-    error in units of the helper's tolerance (rtol 1e-11, atol 1e-12) before anything the helper found is raised.
-    Returns (the engines' report, outs)."""
+def _diag_replay(c, label, **step_kw):
+    """The memoised oracle chain of ``c`` on the device under Rules.diag(); prints checked / skipped, the worst position error
+    in units of the tolerance (rtol 1e-11, atol 1e-12) and the kernels that ran. Returns (the device's iterations, outs)."""
     snaps, outs = GO.oracle_chain(c)
     step, _start = GO.device_step(c, **step_kw)
-    ran = _Ran(step)
+    ran = run_snapshots(step, snaps)
+    res = assert_replay(ran, snaps, outs, GO.rules(c), label)
     total = c.tune + c.draws
-    checked = fragile = None
-    try:
-        checked, fragile = replay_iterations_on_device(step, snaps, outs, label=label, expect_plan=expect_plan)
-    finally:
-        worst = float("nan")
-        if sum(len(e["q"]) for e in ran.engines) == total:
-            keep = [i for i, o in enumerate(outs) if GO.oracle_margin(c, o) >= GO.FLOOR]
-            want = np.array([outs[i]["q"] for i in keep])
-            worst = float(np.max(np.abs(ran.q()[keep] - want) / (1e-12 + 1e-11 * np.abs(want))))
-        print("%s: checked %s skipped %s of %d; worst position error %.4g of the tolerance; plan %s leaf group %s general %s "
-              "shape %s" % (label, checked, fragile, total, worst, sorted(map(str, ran.kernels("plan"))),
-                            sorted(map(str, ran.kernels("leaf"))), sorted(ran.kernels("wide")), sorted(ran.kernels("shape"))))
-    assert checked + fragile == total
-    assert checked >= total - (2 if total >= 30 else 1), (label, checked, fragile)
+    print("%s: checked %s skipped %s of %d; worst position error %.4g of the tolerance; plan %s leaf group %s general %s "
+          "shape %s" % (label, res.checked, res.skipped, total, res.worst_q, sorted(map(str, ran.kernels("plan"))),
+                        sorted(map(str, ran.kernels("leaf"))), sorted(ran.kernels("wide")), sorted(ran.kernels("shape"))))
+    assert res.checked + res.skipped == total
+    assert res.checked >= total - (2 if total >= 30 else 1), (label, res)
     assert len(ran.engines) == 2      # the tuning iterations and the draws
     return ran, outs
 
@@ -116,7 +61,7 @@ def test_fused_kernels_replay_the_oracle(monkeypatch, c, plan, leaf):
     else:
         monkeypatch.setenv("LMC_LEAF_GROUP", leaf)   # struct lmc_tuning.leaf_group, read by the host (engine.tuning_from_env)
     label = "fused %s plan %s leaf %s" % (GO.case_id(c), plan, leaf)
-    ran, outs = _diag_replay(c, label, expect_plan=plan, lds_plan=plan)
+    ran, outs = _diag_replay(c, label, lds_plan=plan)
     ns = M.ns_for(c.d)
     assert ran.kernels("wide") == {False} and ran.kernels("kind") == {"nuts"}, ran.kernels("wide")
     assert {s[1:] for s in ran.kernels("shape")} == {(ns, 1)}, ran.kernels("shape")
@@ -128,18 +73,18 @@ def test_fused_kernels_replay_the_oracle(monkeypatch, c, plan, leaf):
         assert len(div) >= 3, div
         stayed = 0
         for i in div:
-            assert GO.oracle_margin(c, outs[i]) >= GO.FLOOR, i      # none of them is among the skipped
+            assert not GO.rules(c).skips(outs[i]), i      # none of them is among the skipped
             for name in ("diverging", "tree_size", "depth"):
-                assert ran.stat(name)[i] == outs[i]["stats"][name], (label, i, name)
+                assert ran[i]["stats"][name] == outs[i]["stats"][name], (label, i, name)
             if np.array_equal(outs[i]["q"], snaps[i]["q"]):
                 stayed += 1
-                np.testing.assert_array_equal(ran.q()[i], snaps[i]["q"], err_msg="%s iter %d" % (label, i))
+                np.testing.assert_array_equal(ran.q[i], snaps[i]["q"], err_msg="%s iter %d" % (label, i))
         print("%s: %d diverging iterations replayed, %d of them stayed at their start" % (label, len(div), stayed))
 
 
 def test_a_prior_scale_off_by_five_parts_in_ten_million_fails_the_replay():
     """The control on the device: the same replay with a targets.GLM whose prior precision is off by 1e-6 relative (the
-    CPU test's third mutant, on every coefficient) is refused by the helper, and at least half of the tuning iterations miss
+    CPU test's third mutant, on every coefficient) is refused by assert_replay, and at least half of the tuning iterations miss
     the position tolerance -- the comparison really is between this device run and that oracle chain."""
     from littlemcmc_amd import targets as T
 
@@ -149,11 +94,10 @@ def test_a_prior_scale_off_by_five_parts_in_ten_million_fails_the_replay():
     assert abs(wrong.tau / GO.TAU - 1.0) < 1.1e-6
     snaps, outs = GO.oracle_chain(c)
     step, _start = GO.device_step(c, target=wrong)
-    ran = _Ran(step)
+    ran = run_snapshots(step, snaps)
     with pytest.raises(AssertionError):
-        replay_iterations_on_device(step, snaps, outs, label="wrong prior scale")
-    got = ran.engines[0]["q"]                     # the tuning iterations: the helper stopped there
-    assert len(got) == c.tune
+        assert_replay(ran, snaps, outs, GO.rules(c), "wrong prior scale")
+    got = ran.q[:c.tune]                          # the tuning iterations
     missing = sum(not np.allclose(got[i], outs[i]["q"], rtol=1e-11, atol=1e-12) for i in range(c.tune))
     print("wrong prior scale: %d of %d tuning iterations miss the position tolerance" % (missing, c.tune))
     assert 2 * missing >= c.tune, missing
@@ -190,15 +134,13 @@ def test_hmc_replays_the_oracle(c):
 def _dense_replay(c, expect, label):
     snaps, outs = GO.oracle_chain(c)
     dstep, _start = GO.device_step(c)
-    f32_born = c.kind in GO.F32_BORN
-    assert GO.skip_floor(c) == (DECISION if f32_born else 1e-9)
-    res = replay_dense(dstep, snaps, outs, REPLAY_F32 if f32_born else REPLAY_F64, DECISION if f32_born else 1e-9, label,
-                       expect_kernel=expect)
+    ran = run_snapshots(dstep, snaps)
+    assert ran.kernels("dense") == {expect}, (label, ran.engines)
+    res = assert_replay(ran, snaps, outs, GO.rules(c), label)
     total = c.tune + c.draws
     print("%s: kernel %s; checked %d skipped %d of %d; worst position %.3g / stat %.3g of the tolerance" % (
-        label, expect, res["checked"], res["skipped"], total, res["worst_q"], res["worst_stat"]))
-    assert res["checked"] >= total - 1, res      # TUNE + DRAWS = 19 < 30
-    return res
+        label, expect, res.checked, res.skipped, total, res.worst_q, res.worst_stat))
+    assert res.checked >= total - 1, res      # TUNE + DRAWS = 19 < 30
 
 
 @pytest.mark.parametrize("c", GO.SHARED, ids=GO.case_id)
@@ -219,5 +161,5 @@ def test_per_chain_kernel_replays_the_oracle(c, monkeypatch):
 @pytest.mark.parametrize("c", GO.ADAPT, ids=GO.case_id)
 def test_adapted_dense_matrix_replays_the_oracle(c):
     """init="adapt_full": the estimators, the matrix and its factor go in through set_dense_state per iteration, and the
-    matrix after the iteration is compared with the oracle's next snapshot (replay_dense)."""
+    matrix after the iteration is compared with the oracle's next snapshot (Rules.dense)."""
     _dense_replay(c, "per_chain", "adapt_full %s" % GO.case_id(c))

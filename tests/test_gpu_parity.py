@@ -161,7 +161,7 @@ def test_every_iteration_replay_on_wide_and_multi_wave_shapes(family, d, kw):
     """The kernel shapes beyond one-wave NS<=2 -- NS=4 (d<=256) and teams of 2 / 4 wavefronts per chain
     (d<=512 / d<=1024, LDS exchange + barrier per reduction) -- replayed iteration by iteration against the
     oracle exactly like the golden configurations."""
-    from tests._gpu_util import oracle_chain_snapshots, replay_iterations_on_device
+    from tests._replay import Rules, replay_chain
 
     f = OT.make(family, d)
     tgt = device_target(family, d, f.params())
@@ -170,8 +170,7 @@ def test_every_iteration_replay_on_wide_and_multi_wave_shapes(family, d, kw):
     _s, ostep = orc.init_nuts(f, d, seeds=seeds, **kw)
     start, step = lmc.init_nuts(tgt, d, random_seed=seeds, **kw)
     np.testing.assert_array_equal(_s, start)
-    snaps, outs = oracle_chain_snapshots(ostep, start, seeds[1], tune, draws)
-    checked, fragile = replay_iterations_on_device(step, snaps, outs, label="%s d=%d" % (family, d))
+    checked, fragile = replay_chain(ostep, step, start, seeds[1], tune, draws, Rules.diag(), "%s d=%d" % (family, d))[:2]
     assert checked >= tune + draws - 1, (checked, fragile)
 
 
@@ -179,7 +178,7 @@ def test_growing_adaptation_window_replays_the_reference(golden_dir):
     """QuadPotentialDiagAdapt(adaptation_window=20, adaptation_window_multiplier=2): the window doubles at every
     switch (quadpotential.py:239-243); every iteration of the captured reference chain replayed on the device, the
     per-chain window included, and whole sample() runs agree on the final window."""
-    from tests._gpu_util import oracle_chain_snapshots, replay_iterations_on_device
+    from tests._replay import Rules, assert_replay, record_chain, run_snapshots
 
     g = np.load(os.path.join(golden_dir, "diag_window_multiplier.npz"))
     d, tune, draws, seed = int(g["e2e_d"]), int(g["e2e_tune"]), int(g["e2e_draws"]), int(g["e2e_seed"])
@@ -188,11 +187,11 @@ def test_growing_adaptation_window_replays_the_reference(golden_dir):
     ostep = orc.Step(OT.make("ar1", d), d, kind="nuts", potential=opot)
     pot = lmc.QuadPotentialDiagAdapt(d, start, np.ones(d), 10, adaptation_window=20, adaptation_window_multiplier=2)
     step = lmc.NUTS(lmc.targets.AR1(d), d, potential=pot)
-    snaps, outs = oracle_chain_snapshots(ostep, start, seed, tune, draws)
+    snaps, outs = record_chain(ostep, start, np.random.RandomState(seed), tune, draws)
     np.testing.assert_allclose(np.array([o["q"] for o in outs]), g["e2e_trace"][0], rtol=1e-9, atol=1e-300)
     final = int(g["e2e_final_window"])
     assert sorted(set(s["window"] for s in snaps)) == [20, 40, 80, 160, 320] and final == 320
-    checked, fragile = replay_iterations_on_device(step, snaps, outs, label="growing window")
+    checked, fragile = assert_replay(run_snapshots(step, snaps), snaps, outs, Rules.diag(), "growing window")[:2]
     assert checked >= tune + draws - 2, (checked, fragile)
     trace, stats = lmc.sample(lmc.targets.AR1(d), d, draws=draws, tune=tune, step=step, start=start, chains=3,
                               random_seed=[seed, seed + 1, seed + 2], discard_tuned_samples=False)

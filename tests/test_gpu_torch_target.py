@@ -14,7 +14,8 @@ import littlemcmc_amd as lmc
 from littlemcmc_amd.targets import TorchTarget
 from oracle import lmc_oracle as orc
 from oracle import targets as OT
-from tests._gpu_util import kwargs_from, oracle_chain_snapshots, replay_iterations_on_device
+from tests._gpu_util import kwargs_from
+from tests._replay import Rules, dense_rules, replay_chain
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -70,8 +71,7 @@ def test_every_iteration_of_the_golden_runs_through_ticks(golden_dir, name):
         _s, ostep = orc.init_nuts(f, d, seeds=seeds, **kw)
         _s2, step = lmc.init_nuts(tgt, d, random_seed=seeds, **kw)
         np.testing.assert_array_equal(_s, _s2)
-    snaps, outs = oracle_chain_snapshots(ostep, g["start"], seeds[0], tune, draws)
-    checked, fragile = replay_iterations_on_device(step, snaps, outs, label=name + " (ticks)")
+    checked, fragile = replay_chain(ostep, step, g["start"], seeds[0], tune, draws, Rules.diag(), name + " (ticks)")[:2]
     assert checked >= 0.99 * (tune + draws), (checked, fragile)
 
 
@@ -82,8 +82,7 @@ def test_ticks_on_wide_vectors(d):
     seeds = orc.derive_seeds(99, 2)
     _s, ostep = orc.init_nuts(f, d, seeds=seeds)
     start, step = lmc.init_nuts(tgt, d, random_seed=seeds)
-    snaps, outs = oracle_chain_snapshots(ostep, start, seeds[1], 30, 8)
-    checked, fragile = replay_iterations_on_device(step, snaps, outs, label="ticks d=%d" % d)
+    checked, fragile = replay_chain(ostep, step, start, seeds[1], 30, 8, Rules.diag(), "ticks d=%d" % d)[:2]
     assert checked >= 37, (checked, fragile)
 
 
@@ -214,7 +213,7 @@ def test_graph_replay_of_the_callable_gives_the_same_chains():
 def test_dense_mass_through_ticks_replays_the_reference_chain(golden_dir, name):
     """The captured dense-mass reference chains (tests/golden/e2e_*full*.npz) replayed iteration by iteration with the
     density evaluated by a torch callable: same bar as the fused dense kernel (tests/test_gpu_dense.py)."""
-    from tests.test_gpu_dense import _pot, _replay
+    from tests.test_gpu_dense import _pot
 
     g = np.load(os.path.join(golden_dir, name + ".npz"))
     d, tune, draws = int(g["d"]), int(g["tune"]), int(g["draws"])
@@ -230,7 +229,7 @@ def test_dense_mass_through_ticks_replays_the_reference_chain(golden_dir, name):
         start, ostep = orc.init_nuts(of, d, init=potk, seeds=[seed])
         start_d, dstep = lmc.init_nuts(tgt, d, init=potk, random_seed=[seed])
         np.testing.assert_array_equal(start, start_d)
-    checked = _replay(ostep, dstep, start, seed, tune, draws, potk != "inv", name + " (ticks)")
+    checked = replay_chain(ostep, dstep, start, seed, tune, draws, dense_rules(potk != "inv"), name + " (ticks)").checked
     assert checked >= 0.97 * (tune + draws)
 
 

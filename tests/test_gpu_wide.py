@@ -13,7 +13,8 @@ import littlemcmc_amd as lmc
 from littlemcmc_amd import targets as T
 from oracle import lmc_oracle as orc
 from oracle import targets as OT
-from tests._gpu_util import device_target, kwargs_from, oracle_chain_snapshots, replay_iterations_on_device
+from tests._gpu_util import device_target, kwargs_from
+from tests._replay import REPLAY_F32, Rules, assert_replay, dense_rules, record_chain, replay_chain, run_snapshots
 
 pytestmark = pytest.mark.gpu
 
@@ -42,9 +43,9 @@ def test_model_ndim_2000_every_iteration_of_the_reference_chain(golden_dir):
         assert eng.wide and eng.kernel_shape() == (2, 2, 16)
     finally:
         eng.close()
-    snaps, outs = oracle_chain_snapshots(ostep, start, seeds[0], tune, draws)
+    snaps, outs = record_chain(ostep, start, np.random.RandomState(seeds[0]), tune, draws)
     np.testing.assert_allclose(np.array([o["q"] for o in outs]), g["trace"][0], rtol=1e-9, atol=1e-300)   # oracle == reference
-    checked, fragile = replay_iterations_on_device(step, snaps, outs, label="diag2000")
+    checked, fragile = assert_replay(run_snapshots(step, snaps), snaps, outs, Rules.diag(), "diag2000")[:2]
     print("d = 2000: %d of %d iterations replayed, %d fragile" % (checked, tune + draws, fragile))
     assert checked >= tune + draws - 1
 
@@ -60,8 +61,7 @@ def test_every_iteration_replay_beyond_1024_dimensions(family, d, kw):
     _s, ostep = orc.init_nuts(f, d, seeds=seeds, **kw)
     start, step = lmc.init_nuts(tgt, d, random_seed=seeds, **kw)
     np.testing.assert_array_equal(_s, start)
-    snaps, outs = oracle_chain_snapshots(ostep, start, seeds[1], tune, draws)
-    checked, fragile = replay_iterations_on_device(step, snaps, outs, label="%s d=%d" % (family, d))
+    checked, fragile = replay_chain(ostep, step, start, seeds[1], tune, draws, Rules.diag(), "%s d=%d" % (family, d))[:2]
     assert checked >= tune + draws - 1, (checked, fragile)
 
 
@@ -88,8 +88,6 @@ def test_sample_api_beyond_1024_dimensions():
 
 def test_dense_model_ndim_384_every_iteration_of_the_reference_chain(golden_dir):
     """QuadPotentialFull at d = 384 (quadpotential.py:430-468): the captured reference chain through the general kernel."""
-    from tests.test_gpu_dense import REPLAY_F32, _replay
-
     g = _load(golden_dir, "e2e_nuts_full_ar1_384")
     d, tune, draws = int(g["d"]), int(g["tune"]), int(g["draws"])
     cov = ar1_cov(d, float(g["rho"]))
@@ -98,15 +96,13 @@ def test_dense_model_ndim_384_every_iteration_of_the_reference_chain(golden_dir)
     dstep = lmc.NUTS(T.AR1(d, 0.9), d, potential=lmc.QuadPotentialFull(cov))
     seed = int(g["seeds"][0])
     start = orc.jitter_start(seed, d)      # sample() without start: init_nuts' jitter (sampling.py:148-159)
-    n = _replay(ostep, dstep, start, seed, tune, draws, True, "full d=384")
+    n = replay_chain(ostep, dstep, start, seed, tune, draws, dense_rules(True), "full d=384").checked
     print("dense d = 384: %d of %d iterations replayed (tolerance %g: float32-born momentum)" % (n, tune + draws, REPLAY_F32))
     assert n >= tune + draws - 3
 
 
 @pytest.mark.parametrize("d,kind", [(300, "full"), (520, "inv"), (1100, "full64")])
 def test_dense_fixed_matrices_beyond_256_dimensions(d, kind):
-    from tests.test_gpu_dense import _replay
-
     rs = np.random.RandomState(d)
     a = rs.randn(d, d) / np.sqrt(d)
     mat = a @ a.T + 0.5 * np.eye(d)
@@ -121,7 +117,7 @@ def test_dense_fixed_matrices_beyond_256_dimensions(d, kind):
     dstep = lmc.NUTS(tgt, d, potential=dpot)
     start = 0.1 * rs.randn(d)
     tune, draws = (6, 2) if d > 1000 else (10, 4)
-    n = _replay(ostep, dstep, start, 4242 + d, tune, draws, kind == "full", "%s d=%d" % (kind, d))
+    n = replay_chain(ostep, dstep, start, 4242 + d, tune, draws, dense_rules(kind == "full"), "%s d=%d" % (kind, d)).checked
     assert n >= tune + draws - 2
 
 
@@ -152,10 +148,9 @@ def test_diag_adapt_float64_matches_the_reference(golden_dir):
         opot = orc.DiagAdaptPotential(d, g["start"], np.ones(d), 10, dtype="float64")
         ostep = orc.Step(f, d, kind="nuts", potential=opot)
         step = lmc.NUTS(tgt, d, potential=lmc.QuadPotentialDiagAdapt(d, g["start"], np.ones(d), 10, dtype="float64"))
-        snaps, outs = oracle_chain_snapshots(ostep, g["start"], int(g["seeds"][c]), tune, draws)
+        snaps, outs = record_chain(ostep, g["start"], np.random.RandomState(int(g["seeds"][c])), tune, draws)
         np.testing.assert_allclose(np.array([o["q"] for o in outs]), g["trace"][c], rtol=1e-9, atol=1e-300)
-        checked, fragile = replay_iterations_on_device(step, snaps, outs, label="diag64 chain %d" % c)
-        total += checked
+        total += assert_replay(run_snapshots(step, snaps), snaps, outs, Rules.diag(), "diag64 chain %d" % c).checked
     assert total >= int(g["chains"]) * (tune + draws) - 2
     # ... and through sample(): the state the step object is left with carries the potential's dtype
     step = lmc.NUTS(tgt, d, potential=lmc.QuadPotentialDiagAdapt(d, g["start"], np.ones(d), 10, dtype="float64"))
@@ -171,8 +166,6 @@ def test_full_adapt_float64_matches_the_reference(golden_dir):
     """QuadPotentialFullAdapt(dtype="float64") (quadpotential.py:484,497-509): protocol values, the update() sequence across a
     window switch -- covariance exact, factor to float64 rounding -- and every iteration of the captured reference run, with
     estimators, covariance and factor compared after each tuning iteration."""
-    from tests.test_gpu_dense import _replay
-
     g = _load(golden_dir, "e2e_nuts_adaptfull64_ar1_10")
     d = int(g["d"])
     pot = lmc.QuadPotentialFullAdapt(d, g["unit_initial_mean"], g["unit_initial_cov"], 10, adaptation_window=20, dtype="float64")
@@ -203,7 +196,8 @@ def test_full_adapt_float64_matches_the_reference(golden_dir):
         assert eng.wide and eng.mass_f64
     finally:
         eng.close()
-    assert _replay(ostep, dstep, g["start"], int(g["seeds"][0]), tune, draws, False, "adapt_full float64") >= tune + draws - 2
+    res = replay_chain(ostep, dstep, g["start"], g["seeds"][0], tune, draws, dense_rules(False), "adapt_full float64")
+    assert res.checked >= tune + draws - 2
     # ... and through sample(): the potential the step object is left with carries the dtype
     dstep = lmc.NUTS(tgt, d, potential=lmc.QuadPotentialFullAdapt(d, g["start"], np.eye(d), 10, dtype="float64"))
     trace, stats = lmc.sample(tgt, d, draws=draws, tune=tune, step=dstep, start=g["start"], chains=1,
@@ -216,15 +210,13 @@ def test_full_adapt_float64_matches_the_reference(golden_dir):
 
 def test_full_adapt_float64_at_300_dimensions():
     """The float64 form beyond the fused kernels' sizes too: an oracle chain at d = 300, every iteration."""
-    from tests.test_gpu_dense import _replay
-
     d, seed = 300, 4321
     f = OT.make("ar1", d)
     tgt = device_target("ar1", d, f.params())
     start = orc.jitter_start(seed, d)
     ostep = orc.Step(f, d, kind="nuts", potential=orc.FullAdaptPotential(d, start, np.eye(d), 10, dtype="float64"))
     dstep = lmc.NUTS(tgt, d, potential=lmc.QuadPotentialFullAdapt(d, start, np.eye(d), 10, dtype="float64"))
-    assert _replay(ostep, dstep, start, seed, 10, 2, False, "adapt_full float64 d=300") >= 10
+    assert replay_chain(ostep, dstep, start, seed, 10, 2, dense_rules(False), "adapt_full float64 d=300").checked >= 10
 
 
 def test_fixed_diagonal_in_float64():
@@ -269,16 +261,15 @@ def test_small_goldens_replay_through_the_general_kernel(golden_dir, name, team,
             assert eng.wide and eng.kernel_shape()[2] == team
         finally:
             eng.close()
-        snaps, outs = oracle_chain_snapshots(ostep, g["start"], seeds[c], tune, draws)
-        checked, fragile = replay_iterations_on_device(step, snaps, outs, label="%s (general kernel) chain %d" % (name, c))
-        total += checked
+        total += replay_chain(ostep, step, g["start"], seeds[c], tune, draws, Rules.diag(),
+                              "%s (general kernel) chain %d" % (name, c)).checked
     assert total >= min(chains, 2) * (tune + draws) - 2
 
 
 @pytest.mark.parametrize("team", [1, 16])
 @pytest.mark.parametrize("name", ["e2e_nuts_full_ar1_12", "e2e_nuts_fullinv_ar1_12", "e2e_nuts_full64_ar1_12", "e2e_hmc_full_std10"])
 def test_dense_goldens_replay_through_the_general_kernel(golden_dir, name, team, monkeypatch):
-    from tests.test_gpu_dense import _oracle_and_device_steps, _replay
+    from tests.test_gpu_dense import _oracle_and_device_steps
 
     monkeypatch.setenv("LMC_FORCE_WIDE", "1")
     monkeypatch.setenv("LMC_WIDE_TEAM", str(team))
@@ -286,7 +277,7 @@ def test_dense_goldens_replay_through_the_general_kernel(golden_dir, name, team,
     ostep, dstep, start = _oracle_and_device_steps(g)
     f32_born = str(g["potential"]) not in ("inv", "full64")
     tune, draws = int(g["tune"]), int(g["draws"])
-    n = _replay(ostep, dstep, start, int(g["seeds"][0]), tune, draws, f32_born, name + " (general kernel)")
+    n = replay_chain(ostep, dstep, start, g["seeds"][0], tune, draws, dense_rules(f32_born), name + " (general kernel)").checked
     assert n >= 0.97 * (tune + draws)
 
 
@@ -298,8 +289,6 @@ def test_dense_goldens_replay_through_the_general_kernel(golden_dir, name, team,
 def test_full_adapt_beyond_256_dimensions_replays_the_oracle(d, family):
     """init='jitter+adapt_full' at d = 300 (one wavefront per chain) and d = 520 (the 16-wavefront team): every iteration from
     the oracle's pre-iteration state -- estimators, covariance, factor, window bookkeeping after each tuning iteration."""
-    from tests.test_gpu_dense import _replay
-
     of = OT.make(family, d)
     tgt = device_target(family, d, of.params())
     seed = 900 + d
@@ -312,7 +301,8 @@ def test_full_adapt_beyond_256_dimensions_replays_the_oracle(d, family):
     finally:
         eng.close()
     tune, draws = (12, 3) if d < 1024 else (5, 1)      # (1024: the largest size the potential accepts)
-    assert _replay(ostep, dstep, start, seed, tune, draws, True, "adapt_full d=%d" % d) >= tune + draws - 2
+    res = replay_chain(ostep, dstep, start, seed, tune, draws, dense_rules(True), "adapt_full d=%d" % d)
+    assert res.checked >= tune + draws - 2
 
 
 @pytest.mark.parametrize("name", ["e2e_nuts_adaptfull_ar1_10_a", "e2e_nuts_adaptfull_ar1_10_b", "e2e_nuts_adaptfull_std70"])
@@ -486,8 +476,7 @@ def test_goldens_replay_through_the_wide_tick_kernel(golden_dir, name, monkeypat
         assert eng.wide
     finally:
         eng.close()
-    snaps, outs = oracle_chain_snapshots(ostep, g["start"], seeds[0], tune, draws)
-    checked, fragile = replay_iterations_on_device(step, snaps, outs, label=name + " (wide ticks)")
+    checked, fragile = replay_chain(ostep, step, g["start"], seeds[0], tune, draws, Rules.diag(), name + " (wide ticks)")[:2]
     assert checked >= 0.99 * (tune + draws), (checked, fragile)
 
 
@@ -502,8 +491,7 @@ def test_callables_beyond_1024_dimensions(d):
     tune, draws = 12, 4
     _s, ostep = orc.init_nuts(f, d, seeds=seeds)
     start, step = lmc.init_nuts(torch_ar1(d), d, random_seed=seeds)
-    snaps, outs = oracle_chain_snapshots(ostep, start, seeds[1], tune, draws)
-    checked, fragile = replay_iterations_on_device(step, snaps, outs, label="torch callable d=%d" % d)
+    checked, fragile = replay_chain(ostep, step, start, seeds[1], tune, draws, Rules.diag(), "torch callable d=%d" % d)[:2]
     assert checked >= tune + draws - 1
     if d > 2000:
         return
