@@ -702,6 +702,50 @@ int lmc_glm_pointwise(const double* x, int64_t chains, int64_t draws_stride, int
                       const double* rows, int64_t row_len, int64_t n_rows, int64_t first_chain, int64_t chains_per_group,
                       double* out, void* stream);
 
+/* ---- PSIS-LOO: Pareto-smoothed importance-sampling leave-one-out on the draws in HBM (additive within ABI 9; Vehtari,
+ * Gelman, Gabry 2017; littlemcmc_amd/predictive.py: psis, loo) --------------------------------------------------------------
+ * lmc_glm_pointwise_loglik WRITES the pointwise log-likelihood that lmc_glm_pointwise only reduces. x .. chains_per_group are
+ * the arguments of lmc_glm_pointwise, with one more demand: the trace block holds WHOLE groups, first_chain % chains_per_group
+ * == 0 and chains % chains_per_group == 0 (a row of the result is all the draws of one posterior). With G = chains /
+ * chains_per_group groups in the block, the observation blocks [ob0, ob1) (64 observations a block, 0 <= ob0 < ob1 <=
+ * npad / 64) and S = chains_per_group * n, out is [G][(ob1 - ob0) * 64][S] doubles (DEVICE):
+ *   out[group][(ob - ob0) * 64 + lane][s] = l[s, 64 ob + lane],   s = (chain within the group) * n + t,  t in [0, n)
+ * so every (group, observation) row is S contiguous doubles, chains n apart. l is THE SAME BITS lmc_glm_pointwise reduces
+ * (one device function computes it for both kernels): max_s of a row equals plane [1] of lmc_glm_pointwise exactly. Padding
+ * observations (i >= N) hold finite values of no meaning.
+ * Refused with LMC_ERR_INVALID before any HIP call: what lmc_glm_pointwise refuses before its header copy; a block that does
+ * not hold whole groups; ob0 < 0, ob1 <= ob0, ob1 > npad / 64; chains * (ob1 - ob0) >= 2^31. Then the same header check. */
+int lmc_glm_pointwise_loglik(const double* x, int64_t chains, int64_t draws_stride, int32_t dim, int64_t t0, int64_t n,
+                             const double* rows, int64_t row_len, int64_t n_rows, int64_t first_chain, int64_t chains_per_group,
+                             int64_t ob0, int64_t ob1, double* out, void* stream);
+
+/* PSIS of `rows` independent rows of S log-likelihood values: row r is l[r * row_stride .. + S) (DEVICE, row_stride >= S);
+ * nothing beyond a row's S values is read. The call knows nothing of GLMs. out is [rows][8] doubles (DEVICE):
+ *   [0] elpd   [1] pareto_k   [2] n_tail   [3] sigma (the GPD scale)   [4] ess_w = (sum w)^2 / sum w^2 of the final weights
+ *   [5] the cutoff (a shifted log ratio)   [6] min_s l   [7] 0
+ * One row, with M = tail_len (the host passes min(S / 5, ceil(3 sqrt(S / reff))); for S = 1, M = 0):
+ *  1. lw_s = -l_s - c, c = max_s(-l_s), so max lw = 0. If any l_s is NaN or +-inf: [0], [1], [3], [4], [5] are NaN, [2] = 0
+ *     and [6] is NaN (some NaN) or the plain min; no other row is affected.
+ *  2. cutoff = the (M + 1)-th largest lw, but at least log(DBL_MIN) = -708.3964185322641. The tail is {s : lw_s > cutoff},
+ *     n_tail its size: at most M, fewer when values tie with the cutoff.
+ *  3. n_tail <= 4: k = +inf, sigma = NaN, no smoothing. Otherwise the tail is sorted by ascending lw (equal lw: by descending
+ *     l), x_i = exp(lw_(i)) - exp(cutoff), i = 1 .. n_tail, and the generalised Pareto fit of Zhang and Stephens (2009) with
+ *     the weakly informative priors of Vehtari et al. is: m = 30 + floor(sqrt(n_tail));
+ *     b_j = (1 - sqrt(m / (j - 0.5))) / (3 x_(floor(n_tail / 4 + 0.5))) + 1 / x_(n_tail), j = 1 .. m (1-based order statistics);
+ *     k_j = mean_i log1p(-b_j x_i);  L_j = n_tail (log(-b_j / k_j) - k_j - 1);  w_j = 1 / sum_l exp(L_l - L_j);
+ *     b = sum_j b_j w_j;  k = mean_i log1p(-b x_i);  sigma = -k / b;  finally k <- (n_tail k + 5) / (n_tail + 10).
+ *  4. If k is finite, the i-th smallest tail element's lw becomes log(exp(cutoff) + sigma expm1(-k log1p(-p_i)) / k),
+ *     p_i = (i - 0.5) / n_tail; then every tail lw above 0 is set to 0.
+ *  5. elpd = log sum_s exp(lw_s + l_s) - log sum_s exp(lw_s), evaluated as -c + log A - log B with
+ *     A = (S - n_tail) + sum_tail exp(lw'_i - lw_i)  (lw + l = -c for every draw outside the tail, lw' the smoothed value),
+ *     B = sum_s w_s, w_s = exp(lw_s) the final weights; ess_w = B^2 / sum_s w_s^2. A constant row gives elpd = l exactly.
+ * The cutoff, the tail's membership, n_tail and the order are exact; the sums are taken in a fixed order, so two calls on
+ * the same data give the same bits (no floating-point atomics). One workgroup per row; the sorted tail lives in LDS, hence
+ * LMC_PSIS_MAX_TAIL. Refused with LMC_ERR_INVALID before any HIP call: NULL l or out; rows outside [1, 2^31); S < 1;
+ * row_stride < S; tail_len < 0; tail_len > LMC_PSIS_MAX_TAIL; tail_len >= S when S > 1. */
+#define LMC_PSIS_MAX_TAIL 4096
+int lmc_psis_rows(const double* l, int64_t rows, int64_t S, int64_t row_stride, int32_t tail_len, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

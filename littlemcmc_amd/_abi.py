@@ -20,6 +20,7 @@ TARGET_STD_NORMAL, TARGET_DIAG_GAUSSIAN, TARGET_AR1, TARGET_FUNNEL, TARGET_NORMA
 TARGET_GLM = 8   # (7 is unassigned) additive within ABI 9: a regression posterior that carries its data (include/lmc_hip.h: the row layout)
 GLM_BERNOULLI, GLM_POISSON, GLM_GAUSSIAN = 0, 1, 2
 GLM_MAX_DIM, GLM_HEADER, GLM_MAX_ROW = 512, 8, 1 << 29
+PSIS_MAX_TAIL = 4096   # include/lmc_hip.h: LMC_PSIS_MAX_TAIL, the sorted tail of a row lives in LDS (32 KiB of doubles)
 STATUS_BAD_INITIAL_ENERGY = 1
 SDOT_NATIVE, SDOT_OPENBLAS_SKYLAKEX, SDOT_OPENBLAS_HASWELL = 0, 1, 2
 RNG_NUMPY, RNG_PHILOX, RNG_COUNTER = 0, 1, 2
@@ -201,6 +202,9 @@ _SIGNATURES = {
                                                C.c_int64, _P, _P]),
     "lmc_glm_pointwise": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int64,
                                     C.c_int64, _P, _P]),
+    "lmc_glm_pointwise_loglik": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int64,
+                                           C.c_int64, C.c_int64, C.c_int64, C.c_int64, _P, _P]),
+    "lmc_psis_rows": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _P, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -30,12 +30,11 @@
 #include <vector>
 
 #include "../../include/lmc_hip.h"
+#include "lmc_predict_tile.hpp"
 #include "lmc_targets.hpp"
 
 namespace lmc {
 
-constexpr int kPredT = 8;        // draws per loaded X element (accumulators eta[kPredT])
-constexpr int kPredBatch = 8;    // rows of Xt in flight: the 8 its rows are padded to
 constexpr int kPredPlanes = 6;
 
 static_assert(kGlmHeader == LMC_GLM_HEADER && kGlmMaxDim == LMC_GLM_MAX_DIM, "lmc_targets.hpp and lmc_hip.h agree");
@@ -60,11 +59,6 @@ __device__ __forceinline__ void pw_merge(double na, PwStats& a, double nb, const
     a.mean = a.mean + delta * (nb / n);
     a.M2 = (a.M2 + b.M2) + (delta * delta) * (na * nb / n);
     a.smu = a.smu + b.smu;
-}
-
-typedef const __attribute__((address_space(1))) double* GRow;
-__device__ __forceinline__ double grow_at(GRow base, unsigned bytes) {
-    return *reinterpret_cast<GRow>(reinterpret_cast<const __attribute__((address_space(1))) char*>(base) + bytes);
 }
 
 __global__ __launch_bounds__(64) void pointwise_kernel(const double* __restrict__ x, long long chains, long long draws_stride,
@@ -98,64 +92,10 @@ __global__ __launch_bounds__(64) void pointwise_kernel(const double* __restrict_
         const double* xc = x + (c * draws_stride + t0) * dim;
         for (long long t = 0; t < n; t += kPredT) {
             const int k = (n - t < kPredT) ? static_cast<int>(n - t) : kPredT;   // draws of this tile (wave-uniform)
-            // a tile's missing draws repeat its last one (a valid row; their values are deselected below)
-            const double* qt = xc + t * dim;
-            int qoff[kPredT];
-#pragma unroll
-            for (int i = 0; i < kPredT; ++i) qoff[i] = (i < k ? i : k - 1) * dim;
-            double eta[kPredT];
-#pragma unroll
-            for (int i = 0; i < kPredT; ++i) eta[i] = 0.0;
-            unsigned col = col0;
-            int e0 = 0;
-            for (; e0 + kPredBatch <= dim; e0 += kPredBatch) {
-                double xv[kPredBatch];
-#pragma unroll
-                for (int j = 0; j < kPredBatch; ++j) xv[j] = grow_at(xt, col + static_cast<unsigned>(j) * row_bytes);
-#pragma unroll
-                for (int j = 0; j < kPredBatch; ++j)
-#pragma unroll
-                    for (int i = 0; i < kPredT; ++i) eta[i] = __builtin_fma(xv[j], qt[qoff[i] + e0 + j], eta[i]);
-                col += kPredBatch * row_bytes;
-            }
-            if (e0 < dim) {   // the last rows: Xt is padded to 8 rows (zeros), the trace row is NOT: q[e] only for e < dim
-                double xv[kPredBatch];
-#pragma unroll
-                for (int j = 0; j < kPredBatch; ++j) xv[j] = grow_at(xt, col + static_cast<unsigned>(j) * row_bytes);
-#pragma unroll
-                for (int j = 0; j < kPredBatch; ++j) {
-                    const bool have = e0 + j < dim;
-                    const int e = have ? e0 + j : dim - 1;
-#pragma unroll
-                    for (int i = 0; i < kPredT; ++i) {
-                        const double qv = qt[qoff[i] + e];
-                        eta[i] = __builtin_fma(xv[j], have ? qv : 0.0, eta[i]);
-                    }
-                }
-            }
-            // ---- link: the functor's expressions
+            // eta and the link of the tile's draws (lmc_predict_tile.hpp: shared with pointwise_loglik_kernel); a tile's
+            // missing draws repeat its last one and are deselected below
             double l[kPredT], mu[kPredT];
-            if (lik == kGlmBernoulli) {
-#pragma unroll
-                for (int i = 0; i < kPredT; ++i) {
-                    const double ex = exp_lane(-fabs(eta[i]));
-                    mu[i] = ((eta[i] >= 0.0) ? 1.0 : ex) / (1.0 + ex);
-                    l[i] = yn * eta[i] - (fmax(eta[i], 0.0) + log1p_unit(ex));
-                }
-            } else if (lik == kGlmPoisson) {
-#pragma unroll
-                for (int i = 0; i < kPredT; ++i) {
-                    mu[i] = exp_lane(eta[i]);
-                    l[i] = yn * eta[i] - mu[i];
-                }
-            } else {
-#pragma unroll
-                for (int i = 0; i < kPredT; ++i) {
-                    const double res = yn - eta[i];
-                    mu[i] = eta[i];
-                    l[i] = -0.5 * ((res * res) * isig2);
-                }
-            }
+            glm_link_tile(xc + t * dim, k, dim, xt, col0, row_bytes, lik, yn, isig2, l, mu);
             // ---- the tile's statistics
             PwStats tile = {-HUGE_VAL, 0.0, 0.0, 0.0, 0.0};
             double sum = 0.0;
@@ -218,16 +158,6 @@ __global__ void pointwise_reduce_kernel(const double* __restrict__ partial, int 
     o[5LL * npad] = acc.smu;
 }
 
-// npad of a GLM row of row_len doubles at dimension dim, or 0 if no N gives that length (pure arithmetic)
-static int64_t glm_npad_of_row(int64_t row_len, int32_t dim) {
-    int64_t ns = 1;
-    while (ns * 64 < dim) ns *= 2;
-    const int64_t per_obs = 1 + (dim + 7) / 8 * 8 + 64 * ns;
-    if (row_len <= LMC_GLM_HEADER || row_len >= LMC_GLM_MAX_ROW || (row_len - LMC_GLM_HEADER) % per_obs != 0) return 0;
-    const int64_t npad = (row_len - LMC_GLM_HEADER) / per_obs;
-    return (npad % 64 == 0) ? npad : 0;
-}
-
 }  // namespace lmc
 
 // See include/lmc_hip.h. x, rows and out are DEVICE pointers on the current device; the work is enqueued on `stream`.
@@ -259,23 +189,8 @@ extern "C" int lmc_glm_pointwise(const double* x, int64_t chains, int64_t draws_
     if (blocks >= lim || (total + 255) / 256 >= lim) return LMC_ERR_INVALID;
     hipStream_t s = static_cast<hipStream_t>(stream);
     // the headers of the touched rows: one strided copy, the call's only host look, before anything is launched
-    std::vector<double> hdr(static_cast<size_t>(groups) * LMC_GLM_HEADER);
-    if (hipMemcpy2DAsync(hdr.data(), LMC_GLM_HEADER * sizeof(double), rows + g0 * row_len, static_cast<size_t>(row_len) * sizeof(double),
-                         LMC_GLM_HEADER * sizeof(double), static_cast<size_t>(groups), hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess) {
-        (void)hipGetLastError();
-        return LMC_ERR_HIP;
-    }
-    int64_t ns = 1;
-    while (ns * 64 < dim) ns *= 2;
-    for (int64_t i = 0; i < groups; ++i) {
-        const double* h = hdr.data() + i * LMC_GLM_HEADER;
-        const bool lik_ok = h[0] == LMC_GLM_BERNOULLI || h[0] == LMC_GLM_POISSON || h[0] == LMC_GLM_GAUSSIAN;
-        const bool n_ok = h[1] >= 1.0 && h[1] <= static_cast<double>(npad) && h[1] > static_cast<double>(npad - 64);
-        if (!lik_ok || !n_ok || h[2] != static_cast<double>(npad) || h[5] != static_cast<double>(dim) ||
-            h[6] != static_cast<double>(64 * ns))
-            return LMC_ERR_INVALID;
-    }
+    const int hdr_rc = glm_check_headers(rows, row_len, g0, groups, npad, dim, s);
+    if (hdr_rc != LMC_OK) return hdr_rc;
     double* partial = nullptr;
     const size_t bytes = static_cast<size_t>(blocks) * kPredPlanes * 64 * sizeof(double);
     if (hipMallocAsync(reinterpret_cast<void**>(&partial), bytes, s) != hipSuccess) return LMC_ERR_HIP;

@@ -1,0 +1,126 @@
+// The eta / link tile of the pointwise predictive kernels, stated ONCE: pointwise_kernel (lmc_predict.hip) reduces the
+// l[], mu[] it returns to the six planes, pointwise_loglik_kernel (lmc_psis.hip) writes the same l[] out -- the same
+// instructions on the same operands, so the written array holds the bits the planes were reduced from.
+//
+// One wavefront, lane = observation (the Xt[e][n] section of the GLM row: one coalesced 512-byte row per coefficient and
+// block of 64 observations). A tile is kPredT consecutive draws of one chain: the trace row q is read through a wave-uniform
+// address (the scalar unit, one load for 64 lanes) and NEVER beyond its d coefficients -- the trace is [.., d], the next
+// doubles are the next draw -- and every loaded X element feeds kPredT FMAs, eta[i] = fma(Xt[e][n], q_i[e], eta[i]) with e
+// ascending: the functor's eta (lmc_targets.hpp: GLMTarget), bit for bit. Then the link, the functor's expressions.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <vector>
+
+#include "../../include/lmc_hip.h"
+#include "lmc_targets.hpp"
+
+namespace lmc {
+
+constexpr int kPredT = 8;        // draws per loaded X element (accumulators eta[kPredT])
+constexpr int kPredBatch = 8;    // rows of Xt in flight: the 8 its rows are padded to
+
+typedef const __attribute__((address_space(1))) double* GRow;
+__device__ __forceinline__ double grow_at(GRow base, unsigned bytes) {
+    return *reinterpret_cast<GRow>(reinterpret_cast<const __attribute__((address_space(1))) char*>(base) + bytes);
+}
+
+// qt: the tile's first draw (dim doubles a draw), k <= kPredT draws of it exist (wave-uniform); xt: the row's Xt section,
+// col0 the lane's byte offset in a row of it, row_bytes = npad * 8; yn the lane's y. l[i], mu[i] for i >= k repeat draw k - 1.
+__device__ __forceinline__ void glm_link_tile(const double* qt, int k, int dim, GRow xt, unsigned col0, unsigned row_bytes,
+                                              int lik, double yn, double isig2, double (&l)[kPredT], double (&mu)[kPredT]) {
+    // a tile's missing draws repeat its last one (a valid row; the callers deselect their values)
+    int qoff[kPredT];
+#pragma unroll
+    for (int i = 0; i < kPredT; ++i) qoff[i] = (i < k ? i : k - 1) * dim;
+    double eta[kPredT];
+#pragma unroll
+    for (int i = 0; i < kPredT; ++i) eta[i] = 0.0;
+    unsigned col = col0;
+    int e0 = 0;
+    for (; e0 + kPredBatch <= dim; e0 += kPredBatch) {
+        double xv[kPredBatch];
+#pragma unroll
+        for (int j = 0; j < kPredBatch; ++j) xv[j] = grow_at(xt, col + static_cast<unsigned>(j) * row_bytes);
+#pragma unroll
+        for (int j = 0; j < kPredBatch; ++j)
+#pragma unroll
+            for (int i = 0; i < kPredT; ++i) eta[i] = __builtin_fma(xv[j], qt[qoff[i] + e0 + j], eta[i]);
+        col += kPredBatch * row_bytes;
+    }
+    if (e0 < dim) {   // the last rows: Xt is padded to 8 rows (zeros), the trace row is NOT: q[e] only for e < dim
+        double xv[kPredBatch];
+#pragma unroll
+        for (int j = 0; j < kPredBatch; ++j) xv[j] = grow_at(xt, col + static_cast<unsigned>(j) * row_bytes);
+#pragma unroll
+        for (int j = 0; j < kPredBatch; ++j) {
+            const bool have = e0 + j < dim;
+            const int e = have ? e0 + j : dim - 1;
+#pragma unroll
+            for (int i = 0; i < kPredT; ++i) {
+                const double qv = qt[qoff[i] + e];
+                eta[i] = __builtin_fma(xv[j], have ? qv : 0.0, eta[i]);
+            }
+        }
+    }
+    // ---- link: the functor's expressions
+    if (lik == kGlmBernoulli) {
+#pragma unroll
+        for (int i = 0; i < kPredT; ++i) {
+            const double ex = exp_lane(-fabs(eta[i]));
+            mu[i] = ((eta[i] >= 0.0) ? 1.0 : ex) / (1.0 + ex);
+            l[i] = yn * eta[i] - (fmax(eta[i], 0.0) + log1p_unit(ex));
+        }
+    } else if (lik == kGlmPoisson) {
+#pragma unroll
+        for (int i = 0; i < kPredT; ++i) {
+            mu[i] = exp_lane(eta[i]);
+            l[i] = yn * eta[i] - mu[i];
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < kPredT; ++i) {
+            const double res = yn - eta[i];
+            mu[i] = eta[i];
+            l[i] = -0.5 * ((res * res) * isig2);
+        }
+    }
+}
+
+// npad of a GLM row of row_len doubles at dimension dim, or 0 if no N gives that length (pure arithmetic)
+inline int64_t glm_npad_of_row(int64_t row_len, int32_t dim) {
+    int64_t ns = 1;
+    while (ns * 64 < dim) ns *= 2;
+    const int64_t per_obs = 1 + (dim + 7) / 8 * 8 + 64 * ns;
+    if (row_len <= LMC_GLM_HEADER || row_len >= LMC_GLM_MAX_ROW || (row_len - LMC_GLM_HEADER) % per_obs != 0) return 0;
+    const int64_t npad = (row_len - LMC_GLM_HEADER) / per_obs;
+    return (npad % 64 == 0) ? npad : 0;
+}
+
+// The headers of the rows [g0, g0 + groups) of a DEVICE table: one strided copy on s, the entry points' only host look,
+// before anything is launched. LMC_ERR_INVALID for a header that disagrees with dim or row_len (npad) or carries an
+// unknown likelihood code.
+inline int glm_check_headers(const double* rows, int64_t row_len, int64_t g0, int64_t groups, int64_t npad, int32_t dim,
+                             hipStream_t s) {
+    std::vector<double> hdr(static_cast<size_t>(groups) * LMC_GLM_HEADER);
+    if (hipMemcpy2DAsync(hdr.data(), LMC_GLM_HEADER * sizeof(double), rows + g0 * row_len, static_cast<size_t>(row_len) * sizeof(double),
+                         LMC_GLM_HEADER * sizeof(double), static_cast<size_t>(groups), hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess) {
+        (void)hipGetLastError();
+        return LMC_ERR_HIP;
+    }
+    int64_t ns = 1;
+    while (ns * 64 < dim) ns *= 2;
+    for (int64_t i = 0; i < groups; ++i) {
+        const double* h = hdr.data() + i * LMC_GLM_HEADER;
+        const bool lik_ok = h[0] == LMC_GLM_BERNOULLI || h[0] == LMC_GLM_POISSON || h[0] == LMC_GLM_GAUSSIAN;
+        const bool n_ok = h[1] >= 1.0 && h[1] <= static_cast<double>(npad) && h[1] > static_cast<double>(npad - 64);
+        if (!lik_ok || !n_ok || h[2] != static_cast<double>(npad) || h[5] != static_cast<double>(dim) ||
+            h[6] != static_cast<double>(64 * ns))
+            return LMC_ERR_INVALID;
+    }
+    return LMC_OK;
+}
+
+}  // namespace lmc

@@ -20,6 +20,8 @@ from . import diagnostics
 
 PLANES = ("n", "m", "S", "mean", "M2", "sum_mu")
 HIGH_VARIANCE = 0.4   # p_waic_i beyond which WAIC is unreliable for that observation (Vehtari, Gelman, Gabry 2017)
+BAD_K = 0.7           # Pareto shape beyond which the PSIS-LOO estimate of that observation is unreliable (the same paper)
+PSIS_COLUMNS = ("elpd", "pareto_k", "n_tail", "sigma", "ess_w", "cutoff", "min_loglik", "reserved")   # lmc_psis_rows: out[.][8]
 
 _device_rows = weakref.WeakKeyDictionary()   # target -> {device: its parameter table in HBM}
 
@@ -224,4 +226,227 @@ def waic(x, target, data=None, **kw):
     out["waic"] = -2.0 * out["elpd_waic"]
     out["n_high_variance"] = (out["p_waic"] > HIGH_VARIANCE).sum(dim=-1)
     out["lppd_total"] = out["lppd"].sum(dim=-1)
+    return out
+
+
+# ---- PSIS-LOO (csrc/lmc_psis.hip; include/lmc_hip.h states the row algorithm) ---------------------------------------------
+def tail_len(S, reff=1.0):
+    """M of a row of S draws at relative efficiency ``reff``: ``min(S // 5, ceil(3 sqrt(S / reff)))`` (Vehtari et al.)."""
+    import math
+
+    S, reff = int(S), float(reff)
+    if not (reff > 0.0) or math.isinf(reff):
+        raise ValueError("reff is one positive number, the relative efficiency ESS / S of the draws (got %r)" % (reff,))
+    return min(S // 5, int(math.ceil(3.0 * math.sqrt(S / reff))))
+
+
+def _checked_tail_len(S, reff):
+    from . import _abi
+
+    M = tail_len(S, reff)
+    if M > _abi.PSIS_MAX_TAIL:
+        raise ValueError("PSIS of %d draws per posterior at reff=%g needs a tail of M = %d values; the kernel sorts at most %d "
+                         "in LDS (LMC_PSIS_MAX_TAIL: about 1.86 million draws at reff=1). Pass fewer draws, e.g. x[:, ::k]"
+                         % (S, reff, M, _abi.PSIS_MAX_TAIL))
+    return M
+
+
+def _hip_psis(l2, M):
+    """One call of lmc_psis_rows: l2[rows, S] (float64, last axis contiguous, on a ROCm device) -> [rows, 8]."""
+    from . import _abi
+
+    lib = _abi.load()
+    rows, S = l2.shape
+    stride = l2.stride(0) if rows > 1 else S
+    out = torch.empty((rows, len(PSIS_COLUMNS)), dtype=torch.float64, device=l2.device)
+    with torch.cuda.device(l2.device):
+        stream = torch.cuda.current_stream(l2.device).cuda_stream
+        rc = lib.lmc_psis_rows(ctypes.c_void_p(l2.data_ptr()), rows, S, stride, int(M), ctypes.c_void_p(out.data_ptr()),
+                               ctypes.c_void_p(stream))
+    if rc != 0:
+        raise RuntimeError("lmc_psis_rows failed (status %d)" % rc)
+    return out
+
+
+def _psis_block(l2, M, psis_fn):
+    if psis_fn is not None:
+        return psis_fn(l2, M)
+    return _hip_psis(l2, M)
+
+
+def psis(loglik, reff=1.0, psis_fn=None):
+    """Pareto-smoothed importance sampling of every row of ``loglik[..., S]`` (a float64 ROCm tensor with a contiguous last
+    axis: S log-likelihood values of one observation under S posterior draws) by the HIP kernel ``lmc_psis_rows``
+    (include/lmc_hip.h states the algorithm). It knows nothing of GLMs: any log-likelihood tensor on the device will do.
+    Returns a dict of tensors shaped ``[...]``: ``elpd_i`` (the leave-one-out log predictive density of the observation,
+    additive constants as in ``loglik``), ``pareto_k`` (the Pareto shape: above ``BAD_K`` = 0.7 the estimate is unreliable;
+    ``inf`` when the tail has fewer than 5 values), ``n_tail``, ``ess_w`` (the effective sample size of the final weights),
+    ``sigma`` (the Pareto scale) and ``min_loglik``.
+
+    ``reff``: ONE positive number, the relative efficiency ``ESS / S`` of the draws; it sets the tail length
+    ``M = min(S // 5, ceil(3 sqrt(S / reff)))``. The default 1.0 is that of independent draws: pass ``ess / S`` of an MCMC
+    run. ``M`` above 4096 -- S above about 1.86 million -- is refused with a ValueError. ``psis_fn(l2[rows, S], M) ->
+    [rows, 8]`` replaces the HIP call (tests of the host logic only)."""
+    if loglik.dim() < 1 or int(loglik.shape[-1]) < 1:
+        raise ValueError("loglik must be [..., S] with S >= 1")
+    S = int(loglik.shape[-1])
+    M = _checked_tail_len(S, reff)
+    if psis_fn is None:
+        if not loglik.is_cuda:
+            from ._abi import HipLibraryError
+
+            raise HipLibraryError("psis() runs on a log-likelihood tensor in HBM (a ROCm tensor); got a CPU tensor and there "
+                                  "is no host implementation")
+        if loglik.dtype != torch.float64:
+            raise ValueError("loglik must be float64 (got %s)" % loglik.dtype)
+    lead = tuple(loglik.shape[:-1])
+    if loglik.dim() == 2 and (S == 1 or loglik.stride(1) == 1) and loglik.stride(0) >= S:
+        l2 = loglik
+    else:
+        if S > 1 and loglik.stride(-1) != 1:
+            raise ValueError("loglik must have a contiguous last axis (stride %d)" % loglik.stride(-1))
+        l2 = loglik.reshape(-1, S)
+        if not l2.is_contiguous():
+            l2 = l2.contiguous()
+    if l2.shape[0] == 0:
+        raise ValueError("loglik holds no row")
+    out = _psis_block(l2, M, psis_fn)
+    names = {"elpd_i": 0, "pareto_k": 1, "n_tail": 2, "sigma": 3, "ess_w": 4, "min_loglik": 6}
+    return {k: out[:, i].reshape(lead) for k, i in names.items()}
+
+
+def _hip_loglik(x, table, first_chain, per, ob0, ob1):
+    """One call of lmc_glm_pointwise_loglik: x[chains, draws, d] holding whole groups -> [groups, 64 (ob1 - ob0), per * draws]."""
+    from . import _abi
+
+    lib = _abi.load()
+    c, n, d = x.shape
+    stride = x.stride(0) // d if c > 1 else n
+    n_rows, row_len = table.shape
+    out = torch.empty((c // per, 64 * (ob1 - ob0), per * n), dtype=torch.float64, device=x.device)
+    with torch.cuda.device(x.device):
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        rc = lib.lmc_glm_pointwise_loglik(ctypes.c_void_p(x.data_ptr()), c, stride, d, 0, n, ctypes.c_void_p(table.data_ptr()),
+                                          row_len, n_rows, int(first_chain), int(per), int(ob0), int(ob1),
+                                          ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(stream))
+    if rc != 0:
+        raise RuntimeError("lmc_glm_pointwise_loglik failed (status %d)" % rc)
+    return out
+
+
+def _loo_plan(x, target):
+    """The blocks of a LOO / pointwise_loglik job: (members, blocks, firsts, per, n_draws, table)."""
+    from .targets import Batched
+
+    members = _members(target)
+    if diagnostics._group_active(None):
+        raise ValueError("PSIS-LOO is a one-process matter: an active process group (sample_distributed) is not supported")
+    blocks = list(x) if isinstance(x, (list, tuple)) else [x]
+    if not blocks or any(b.dim() != 3 for b in blocks):
+        raise ValueError("x must be [chains, draws, d] or a list of such blocks")
+    held = [b for b in blocks if b.shape[0] > 0]
+    if not held:
+        raise ValueError("x holds no chain")
+    if len({(int(b.shape[1]), int(b.shape[2])) for b in held}) > 1:
+        raise ValueError("the chain blocks differ in draws per chain or in d: %s" % [tuple(b.shape[1:]) for b in held])
+    n_draws, d = int(held[0].shape[1]), int(held[0].shape[2])
+    if d != members[0].d:
+        raise ValueError("x has d = %d, the target d = %d" % (d, members[0].d))
+    if n_draws < 1:
+        raise ValueError("x holds no draw")
+    chains = sum(int(b.shape[0]) for b in blocks)
+    per = target.group_size(chains) if isinstance(target, Batched) else chains
+    firsts, f = [], 0
+    for b in blocks:
+        firsts.append(f)
+        f += int(b.shape[0])
+    if any(f % per != 0 for f in firsts):
+        raise ValueError("PSIS-LOO at %d chains per group: a group straddles two chain blocks (blocks of %s chains); the "
+                         "draws of one posterior form one row and need to lie on one device"
+                         % (per, [int(b.shape[0]) for b in blocks]))
+    table = np.ascontiguousarray(target.params, dtype=np.float64).reshape(len(members), -1)
+    return members, blocks, firsts, per, n_draws, table
+
+
+def _loglik_block(b, target, table, first, per, ob0, ob1, loglik_fn):
+    if loglik_fn is not None:
+        return loglik_fn(b, table, first, per, ob0, ob1)
+    b = diagnostics._device_block(b)
+    return _hip_loglik(b, _table_on(target, table, b.device, True), first, per, ob0, ob1)
+
+
+def pointwise_loglik(x, target, groups=None, obs_blocks=None, loglik_fn=None):
+    """The pointwise log-likelihood array itself, ``[G', 64 * blocks, S]`` on the device: ``out[g, i, s]`` is ``l`` of
+    observation ``64 * ob0 + i`` of group ``g`` under draw ``s = (chain within the group) * draws + t`` -- the bits that
+    :func:`pointwise_stats` reduces (additive constants dropped; observations beyond N are padding). It is N / d times the
+    trace: meant for tests and small jobs, :func:`loo` walks it in chunks. ``groups=(g0, g1)`` and ``obs_blocks=(ob0, ob1)``
+    select half-open ranges of groups and of blocks of 64 observations (default: all). ``x`` as for :func:`waic`; with a
+    list of per-GPU blocks every group must lie in one block, and the result is gathered on the first block's device."""
+    members, blocks, firsts, per, n_draws, table = _loo_plan(x, target)
+    nob = (members[0].n_obs + 63) // 64
+    g_lo, g_hi = (0, len(members)) if groups is None else (int(groups[0]), int(groups[1]))
+    ob0, ob1 = (0, nob) if obs_blocks is None else (int(obs_blocks[0]), int(obs_blocks[1]))
+    if not (0 <= g_lo < g_hi <= len(members)) or not (0 <= ob0 < ob1 <= nob):
+        raise ValueError("groups=%r of %d, obs_blocks=%r of %d: half-open, non-empty ranges" % (groups, len(members), obs_blocks, nob))
+    parts = []
+    for b, f in zip(blocks, firsts):
+        lo, hi = max(g_lo, f // per), min(g_hi, (f + int(b.shape[0])) // per)
+        if lo < hi:
+            parts.append(_loglik_block(b[lo * per - f:hi * per - f], target, table, lo * per, per, ob0, ob1, loglik_fn))
+    if not parts:
+        raise ValueError("groups=%r lie in no block of x" % (groups,))
+    return parts[0] if len(parts) == 1 else torch.cat([p.to(parts[0].device) for p in parts], dim=0)
+
+
+def loo(x, target, reff=1.0, scratch_bytes=1 << 30, psis_fn=None, loglik_fn=None, data=None, **kw):
+    """PSIS-LOO of a ``GLM`` (leading axis 1) or of every posterior of a ``Batched`` of GLMs (leading axis G) from the draws in
+    HBM, without a refit: everything :func:`waic` returns (the existing pass; ``**kw`` goes to it), plus per observation
+    ``elpd_loo_i[G, N]`` (the leave-one-out log predictive density, ``GLM.loglik_constant()`` added), ``pareto_k[G, N]``
+    (above ``BAD_K`` = 0.7 the estimate of that observation cannot be trusted -- the per-point answer to ``n_high_variance``),
+    ``n_tail[G, N]``, ``ess_w[G, N]``, and per posterior ``elpd_loo[G]``, ``p_loo[G] = lppd_total - elpd_loo``,
+    ``se_loo[G] = sqrt(N var_n(elpd_loo_i))``, ``looic[G] = -2 elpd_loo`` and ``n_bad_k[G]``. ``reff`` as for :func:`psis`.
+
+    The pointwise log-likelihood (``lmc_glm_pointwise_loglik``) is written to a scratch array of at most ``scratch_bytes`` and
+    smoothed row by row (``lmc_psis_rows``), in chunks of whole groups or, where one group exceeds the scratch, of blocks of
+    64 observations of one group; one such block is ``64 * S * 8`` bytes and must fit. Rows are independent, so the chunking
+    does not change a bit of the result. ``x`` is one tensor or the list of per-GPU blocks of the job (every group within one
+    block): each block runs on its own device and the ``[G, N]`` results are gathered on the first block's device. LOO is
+    in-sample: ``data=`` is refused (score held-out data with :func:`waic`). ``psis_fn`` / ``loglik_fn(x, table, first_chain,
+    per, ob0, ob1)`` replace the two HIP calls (tests of the chunking and finalise logic)."""
+    if data is not None:
+        raise ValueError("loo() is in-sample: leave-one-out of the training data has no data= (waic(x, data=...) scores "
+                         "held-out points)")
+    members, blocks, firsts, per, n_draws, table = _loo_plan(x, target)
+    S = per * n_draws
+    M = _checked_tail_len(S, reff)
+    n_obs = members[0].n_obs
+    nob = (n_obs + 63) // 64
+    unit = 64 * S * 8
+    if unit > int(scratch_bytes):
+        raise ValueError("scratch_bytes=%d is below one block of 64 observations of one posterior: 64 x %d draws x 8 = %d "
+                         "bytes needed" % (int(scratch_bytes), S, unit))
+    cap = int(scratch_bytes) // unit
+    out = waic(x, target, **kw)
+    dev = out["lppd"].device
+    rows = torch.empty((len(members), nob * 64, len(PSIS_COLUMNS)), dtype=torch.float64, device=dev)
+    for b, f in zip(blocks, firsts):   # each block on its own device; the small results move to the first one
+        g_b, n_g = f // per, int(b.shape[0]) // per
+        if cap >= nob:
+            chunks = [(g, min(g + cap // nob, n_g), 0, nob) for g in range(0, n_g, cap // nob)]
+        else:
+            chunks = [(g, g + 1, ob, min(ob + cap, nob)) for g in range(n_g) for ob in range(0, nob, cap)]
+        for lo, hi, ob0, ob1 in chunks:
+            ll = _loglik_block(b[lo * per:hi * per], target, table, f + lo * per, per, ob0, ob1, loglik_fn)
+            res = _psis_block(ll.reshape(-1, S), M, psis_fn).reshape(hi - lo, (ob1 - ob0) * 64, len(PSIS_COLUMNS))
+            rows[g_b + lo:g_b + hi, ob0 * 64:ob1 * 64] = res.to(dev)
+            del ll
+    rows = rows[:, :n_obs]
+    const = torch.as_tensor(np.stack([m.loglik_constant() for m in members]), dtype=torch.float64).to(dev)
+    e = rows[..., 0] + const
+    out["elpd_loo_i"], out["pareto_k"], out["n_tail"], out["ess_w"] = e, rows[..., 1], rows[..., 2], rows[..., 4]
+    out["elpd_loo"] = e.sum(dim=-1)
+    out["p_loo"] = out["lppd_total"] - out["elpd_loo"]
+    out["se_loo"] = torch.sqrt(n_obs * e.var(dim=-1)) if n_obs > 1 else torch.full_like(out["elpd_loo"], float("nan"))
+    out["looic"] = -2.0 * out["elpd_loo"]
+    out["n_bad_k"] = (out["pareto_k"] > BAD_K).sum(dim=-1)
     return out

@@ -235,6 +235,13 @@ class GLM(DeviceTarget):
 
         return predictive.waic(x, self, **kw)
 
+    def loo(self, x, **kw):
+        """``predictive.loo(x, self, ...)``: PSIS-LOO of the draws ``x`` in HBM (leading axis 1) -- ``elpd_loo``, and per
+        observation ``elpd_loo_i`` and the Pareto shape ``pareto_k`` that says where the estimate can be trusted."""
+        from . import predictive
+
+        return predictive.loo(x, self, **kw)
+
     def __repr__(self):
         return "GLM(%s, N=%d, d=%d)" % (self.likelihood, self.n_obs, self.d)
 
@@ -718,6 +725,13 @@ class Batched(DeviceTarget):
         from . import predictive
 
         return predictive.waic(x, self, **kw)
+
+    def loo(self, x, **kw):
+        """``predictive.loo(x, self, ...)`` per posterior (GLM members): PSIS-LOO ``elpd_loo[G]``, ``elpd_loo_i[G, N]``,
+        ``pareto_k[G, N]``, ``n_bad_k[G]``, ... of all groups from the draws in HBM, without a refit."""
+        from . import predictive
+
+        return predictive.loo(x, self, **kw)
 
     def __repr__(self):
         return "Batched(%d x %s, d=%d)" % (self.groups, type(self.members[0]).__name__, self.d)
