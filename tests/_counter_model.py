@@ -1,7 +1,8 @@
 """Host model of the counter-based streams (rng="counter", include/lmc_hip.h: LMC_RNG_COUNTER): Philox4x32-10, the decision
 uniforms u_k, the words behind the momentum normals with the Box-Muller evaluated in float64, and CounterRng -- a
 duck-typed stand-in for np.random.RandomState that hands the oracle the stream's values, which makes the unchanged
-oracle (oracle/lmc_oracle.py threads its rng explicitly) an exact model of the mode."""
+oracle (oracle/lmc_oracle.py threads its rng explicitly) an exact model of the mode. MomentumOnlyRng is the same for
+momentum_rng="philox" (LMC_RNG_PHILOX): the stream's normals, numpy's own uniforms."""
 import numpy as np
 
 M32 = 0xFFFFFFFF
@@ -118,3 +119,57 @@ class CounterRng:
 
     def uniform(self, low=0.0, high=1.0):
         return low + (high - low) * self._next()
+
+
+MT_N = 624   # words of one MT19937 generation; a uniform (random_sample) consumes two
+
+
+class MomentumOnlyRng:
+    """The oracle's rng under momentum_rng="philox" (include/lmc_hip.h: LMC_RNG_PHILOX): ``normal(size)`` is iteration
+    ``first + t``'s row of ``normals_by_iteration`` (the model's normals(), or the device's as fetched with
+    Engine.counter_draws) and leaves the generator alone; ``rand()`` / ``uniform()`` / ``get_state()`` are ONE
+    np.random.RandomState(seed), numpy's legacy stream. Each ``normal()`` starts the next iteration; per finished iteration
+    the uniforms consumed and whether they crossed a twist (position before + 2 x uniforms > 624) are recorded."""
+
+    def __init__(self, seed, normals_by_iteration, first=0):
+        self.seed = int(seed) & M32
+        self._rs = np.random.RandomState(self.seed)
+        self._normals = normals_by_iteration
+        self.git = int(first) - 1
+        self.k = 0
+        self.consumed = []     # uniforms consumed by every finished iteration
+        self.crossed = []      # ... and whether they crossed a twist
+        self._pos = None       # the generator's position when the running iteration began
+        self._open = False
+
+    def normal(self, size=None):
+        self._close()
+        self.git += 1
+        self.k = 0
+        z = np.array(self._normals[len(self.consumed)], dtype=np.float64)
+        assert z.shape == np.empty(size).shape, (z.shape, size)
+        self._pos = int(self._rs.get_state()[2])
+        self._open = True
+        return z
+
+    def _close(self):
+        if self._open:
+            self.consumed.append(self.k)
+            self.crossed.append(self._pos + 2 * self.k > MT_N)
+            self._open = False
+
+    def finish(self):
+        """Close the running iteration; returns (uniforms consumed, twist crossed) per iteration."""
+        self._close()
+        return list(self.consumed), list(self.crossed)
+
+    def rand(self):
+        self.k += 1
+        return self._rs.random_sample()
+
+    def uniform(self, low=0.0, high=1.0):
+        self.k += 1
+        return self._rs.uniform(low, high)
+
+    def get_state(self):
+        return self._rs.get_state()

@@ -4,6 +4,7 @@ pre-iteration state and compared with what the oracle computed from it.
     record_chain      the oracle half: one chain, per iteration the state before it (snapshot) and what came out (output)
     Rules             what a comparison asserts -- THE table of tolerances, skip floors and margins; nothing else states them
     run_snapshots     the device half: one chain per snapshot, one iteration everywhere, everything read back
+    run_keyed_iterations   the device half for a stream keyed by (seed, iteration): K seeded chains, iteration t in one launch
     iteration_errors  one iteration against the rules, pure numpy
     assert_replay     the loop: skip by the rules' margin, raise on the first iteration with an error, count the rest
 
@@ -146,8 +147,9 @@ def dense_rules(f32_born, **kw):
 
 # ---- 3. the device half -------------------------------------------------------------------------------------------------
 class DeviceIterations:
-    """What the device computed, per oracle iteration index i: self[i] = dict(q, stats, after, dense, rng_pos, tune) --
-    ``after`` the chain state and ``dense`` the dense state after the iteration (None where not read), ``tune`` the phase the
+    """What the device computed, per oracle iteration index i: self[i] = dict(q, stats, after, dense, rng_pos, rng, tune) --
+    ``after`` the chain state and ``dense`` the dense state after the iteration (None where not read), ``rng`` the whole
+    generator state after it (get_rng_state's tuple; None where not read) and ``rng_pos`` its position, ``tune`` the phase the
     iteration ran in. ``engines``: per engine, the kernel that ran (plan, leaf, wide, kind, dense, shape, mass_f64)."""
 
     def __init__(self, n):
@@ -157,11 +159,11 @@ class DeviceIterations:
     def __getitem__(self, i):
         return self.iterations[i]
 
-    def put(self, i, c, tune, q, stats, after, dense=None, rng_pos=None):
+    def put(self, i, c, tune, q, stats, after, dense=None, rng_pos=None, rng=None):
         """Iteration i is chain c of what one engine returned."""
         pick = lambda arrays: None if arrays is None else {k: v[c] for k, v in arrays.items()}   # noqa: E731
         self.iterations[i] = dict(q=q[c].copy(), stats=pick(stats), after=pick(after), dense=pick(dense), rng_pos=rng_pos,
-                                  tune=tune)
+                                  rng=rng, tune=tune)
 
     @property
     def q(self):
@@ -213,6 +215,35 @@ def run_snapshots(step, snaps, dense_fields=("cov",)):
                 ran.put(i, c, tune_flag, q, stats, after, dense, eng.get_rng_state(c)[2])
         finally:
             eng.close()
+    return ran
+
+
+def run_keyed_iterations(step, eng, chain_snaps, n_tune, set_rng=False):
+    """The device half for a stream keyed by (seed, iteration) (rng="counter", momentum_rng="philox"; run_snapshots is the
+    MT19937 one): the K seeded chains of ``eng`` take iteration t of every chain in ONE launch, eng.run(n_tune, t, 1), each
+    from its own snapshot chain_snaps[c][t]. ``set_rng``: the chain's MT19937 state is set from the snapshot before the
+    launch (the momentum-only mode: the uniforms are the generator's). The generator state after the launch is kept next
+    to ``after``, whole and as a position. Returns one DeviceIterations per chain; compares nothing."""
+    n_it = len(chain_snaps[0])
+    ran = [DeviceIterations(n_it) for _ in chain_snaps]
+    eng.reserve(n_it, keep_trace=True)
+    for t in range(n_it):
+        now = [snaps[t] for snaps in chain_snaps]
+        eng.set_position(np.stack([s["q"] for s in now]))
+        if set_rng:
+            for c, s in enumerate(now):
+                eng.set_rng_state(c, s["rng"])
+        eng.set_chain_state(chain_state_of(now, eng.mass_f64))
+        eng.run(n_tune, t, 1)
+        assert not eng.status().any()
+        q = eng.trace(t, 1)[:, 0]
+        stats = {k: v[:, 0] for k, v in step._stats_from_engine(eng, t, 1).items()}
+        after = eng.get_chain_state()
+        for c, s in enumerate(now):
+            rng = eng.get_rng_state(c)
+            ran[c].put(t, c, s["tune"], q, stats, after, rng_pos=rng[2], rng=rng)
+    for r in ran:
+        r.engines.append(engine_report(eng))
     return ran
 
 

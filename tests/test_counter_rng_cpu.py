@@ -160,3 +160,82 @@ def test_the_oracle_runs_on_the_counter_stream(kind):
         assert all(1 <= u <= 2 * s + 20 for u, s in zip(used, sizes))
     _q, _s, used_j = run(step_rand=(0.8, 1.2))   # the jitter's uniform is k = 0: one more per iteration on its own stream position
     assert len(used_j) == n_it and min(used_j) >= 2
+
+
+# ---- momentum_rng="philox": MomentumOnlyRng, the oracle's rng of the momentum-only mode ----------------------------------
+def test_momentum_only_rng_uniforms_are_numpys_whatever_normals_lie_between():
+    """rand() / uniform(lo, hi) are np.random.RandomState(seed)'s values bit for bit, in order, however many normal() calls
+    are interleaved; normal() hands out its row and leaves get_state() -- words, position, cached gaussian -- as it was."""
+    seed, d, n_it = 987654321, 7, 30
+    rows = [np.arange(d) + 100.0 * t for t in range(n_it)]
+    rng = cm.MomentumOnlyRng(seed, rows)
+    twin = np.random.RandomState(seed)
+    plan = np.random.RandomState(1)          # how many uniforms every iteration takes, and of which kind
+    want_used = []
+    for t in range(n_it):
+        before = rng.get_state()
+        z = rng.normal(size=d)
+        after = rng.get_state()
+        np.testing.assert_array_equal(z, rows[t])
+        assert z.dtype == np.float64
+        np.testing.assert_array_equal(after[1], before[1])
+        assert after[2:] == before[2:] and after[3] == 0
+        n = int(plan.randint(0, 90))
+        for j in range(n):
+            if j % 3 == 0:
+                assert rng.uniform(0.8, 1.2) == twin.uniform(0.8, 1.2)
+            elif j % 3 == 1:
+                assert rng.rand() == twin.rand()
+            else:
+                assert rng.uniform() == twin.random_sample()
+        want_used.append(n)
+    state, twin_state = rng.get_state(), twin.get_state()
+    np.testing.assert_array_equal(state[1], twin_state[1])
+    assert state[2:] == twin_state[2:]
+    used, crossed = rng.finish()
+    assert used == want_used and len(crossed) == n_it
+    assert crossed[0] == (want_used[0] > 0)          # a freshly seeded generator sits at 624: its first word twists
+    assert sum(crossed) == -(-2 * sum(want_used) // 624)   # every generation begun (no iteration here holds two)
+    with pytest.raises(AssertionError):
+        cm.MomentumOnlyRng(seed, rows).normal(size=d + 1)
+    # the seed is taken as the engine takes it: its low 32 bits
+    assert cm.MomentumOnlyRng(seed + 2 ** 32, rows).rand() == np.random.RandomState(seed).rand()
+
+
+def _pos_after(pos, words):
+    """numpy's legacy MT19937 position after ``words`` 32-bit words from ``pos``: the twist is lazy, 624 stays 624."""
+    end = pos + words
+    return end if end <= 624 else (end - 1) % 624 + 1
+
+
+@pytest.mark.parametrize("d,n_it,n_tune", [(16, 40, 40), (300, 16, 8)])
+def test_the_oracle_runs_on_the_momentum_only_rng(d, n_it, n_tune):
+    """A recorded oracle chain (tests/_replay.record_chain, ar1, the model's normals rounded to float32 as the device's are)
+    on MomentumOnlyRng: every snapshot's generator state is one a team kernel accepts (even position) with no cached
+    gaussian, the state is numpy's own stream at that point, and the twist bookkeeping is the positions' -- iteration t
+    crossed a twist exactly if its words do not fit behind its snapshot's position."""
+    from tests._replay import record_chain
+
+    seed = 20260928 + d
+    f = OT.make("ar1", d)
+    start = orc.jitter_start(seed, d)
+    rows = [cm.normals(seed, t, d).astype(np.float32).astype(np.float64) for t in range(n_it)]
+    rng = cm.MomentumOnlyRng(seed, rows)
+    snaps, outs = record_chain(orc.init_nuts(f, d, seeds=[seed])[1], start, rng, n_tune, n_it - n_tune)
+    used, crossed = rng.finish()
+    assert len(snaps) == len(outs) == len(used) == len(crossed) == n_it
+    twin = np.random.RandomState(seed)
+    for t in range(n_it):
+        name, key, pos, has_gauss, gauss = snaps[t]["rng"]
+        assert name == "MT19937" and pos % 2 == 0 and has_gauss == 0 and gauss == 0.0, (t, pos, has_gauss)
+        tname, tkey, tpos, _hg, _g = twin.get_state()
+        np.testing.assert_array_equal(key, tkey)
+        assert pos == tpos
+        assert used[t] >= 1
+        assert outs[t]["rng_pos"] == _pos_after(pos, 2 * used[t]), t
+        assert crossed[t] == (pos + 2 * used[t] > 624), t
+        assert crossed[t] == (outs[t]["rng_pos"] != pos + 2 * used[t]), t
+        if t + 1 < n_it:
+            assert snaps[t + 1]["rng"][2] == outs[t]["rng_pos"]      # nothing between two iterations touches the generator
+        twin.random_sample(used[t])
+    assert crossed[0] and snaps[0]["rng"][2] == 624

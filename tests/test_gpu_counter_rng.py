@@ -13,7 +13,7 @@ from oracle import targets as OT
 from tests import _counter_model as cm
 from tests import _glm_oracle as GO
 from tests._gpu_util import device_target
-from tests._replay import DeviceIterations, Rules, assert_replay, chain_state_of, engine_report, record_chain
+from tests._replay import Rules, assert_replay, record_chain, run_keyed_iterations
 
 pytestmark = pytest.mark.gpu
 
@@ -91,8 +91,10 @@ CASES = {
 _REPLAYED = {}
 
 
-def _steps(family, d, kind, extra, seeds):
-    """(device step, factory of oracle steps, start)."""
+def _steps(family, d, kind, extra, seeds, mode=(("rng", "counter"),)):
+    """(device step, factory of oracle steps, start). ``mode``: the keyword that selects the stream (this file's is
+    rng="counter"; tests/test_gpu_philox_replay.py builds the same cases with momentum_rng="philox")."""
+    mode = dict(mode)
     if "glm" in extra:   # the float64 statement of the posterior in the device's order, and the targets.GLM of the same cell
         assert family == "glm" and extra["glm"][1] == d
         f, make_target, _info = GO.oracle_glm(*extra["glm"])
@@ -103,41 +105,18 @@ def _steps(family, d, kind, extra, seeds):
     jit = extra.get("jitter")
     start = orc.jitter_start(seeds[0], d)
     if kind == "hmc":
-        step = lmc.HamiltonianMC(tgt, d, rng="counter")
+        step = lmc.HamiltonianMC(tgt, d, **mode)
         ostep = lambda: orc.Step(f, d, kind="hmc", potential=orc.DiagAdaptPotential(d, np.zeros(d), np.ones(d), 10))   # noqa: E731
     elif "scaling" in extra:
         var = np.full(d, extra["scaling"])
-        step = lmc.NUTS(tgt, d, scaling=var, is_cov=True, rng="counter")
+        step = lmc.NUTS(tgt, d, scaling=var, is_cov=True, **mode)
         ostep = lambda: orc.Step(f, d, kind="nuts", scaling=var, is_cov=True)   # noqa: E731
     else:
         kw = {} if jit is None else {"step_rand": lmc.base_hmc.StepRandUniform(*jit)}
-        start_dev, step = lmc.init_nuts(tgt, d, random_seed=seeds, rng="counter", **kw)
+        start_dev, step = lmc.init_nuts(tgt, d, random_seed=seeds, **mode, **kw)
         np.testing.assert_array_equal(start_dev, start)
         ostep = lambda: orc.init_nuts(f, d, seeds=seeds, **({} if jit is None else {"step_rand": jit}))[1]   # noqa: E731
     return step, ostep, start
-
-
-def _run_chains(step, eng, chain_snaps, n_tune):
-    """The device half in the counter layout (tests/_replay.run_snapshots is the MT19937 one): the stream is keyed by (seed,
-    iteration), so the K seeded chains of ``eng`` take iteration t of every chain in one launch, eng.run(n_tune, t, 1).
-    Returns one DeviceIterations per chain; compares nothing."""
-    n_it = len(chain_snaps[0])
-    ran = [DeviceIterations(n_it) for _ in chain_snaps]
-    eng.reserve(n_it, keep_trace=True)
-    for t in range(n_it):
-        now = [snaps[t] for snaps in chain_snaps]
-        eng.set_position(np.stack([s["q"] for s in now]))
-        eng.set_chain_state(chain_state_of(now, eng.mass_f64))
-        eng.run(n_tune, t, 1)
-        assert not eng.status().any()
-        q = eng.trace(t, 1)[:, 0]
-        stats = {k: v[:, 0] for k, v in step._stats_from_engine(eng, t, 1).items()}
-        after = eng.get_chain_state()
-        for c, s in enumerate(now):
-            ran[c].put(t, c, s["tune"], q, stats, after)
-    for r in ran:
-        r.engines.append(engine_report(eng))
-    return ran
 
 
 def _replay(name):
@@ -158,7 +137,7 @@ def _replay(name):
             chains.append(record_chain(make_ostep(), start, rng, n_tune, n_it - n_tune))
             used.append(rng.finish())
         used = np.array(used)                # [K, T] uniforms the oracle consumed
-        ran = _run_chains(step, eng, [snaps for snaps, _outs in chains], n_tune)
+        ran = run_keyed_iterations(step, eng, [snaps for snaps, _outs in chains], n_tune)
         # the chains' MT19937 state was never touched
         for c in range(K):
             now = eng.get_rng_state(c)

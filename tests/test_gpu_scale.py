@@ -544,8 +544,9 @@ def test_dense_adapt_and_tick_paths_sample_the_target_at_scale():
 
 def test_counter_based_momentum_stream_samples_the_target_and_is_partition_invariant():
     """LMC_RNG_PHILOX (NUTS(momentum_rng="philox")): the throughput mode's momentum draw is a pure function of (chain seed,
-    iteration, element). It is NOT the reference's stream -- so no oracle chain to compare with -- and is held to what it
-    promises: the draws have the target's moments at scale (65 536 chains x d = 128 standard normal, every dimension within
+    iteration, element). It is NOT the reference's stream; its oracle replay -- every iteration against the unchanged oracle on
+    the device's own normals and numpy's uniforms -- is tests/test_gpu_philox_replay.py. Here it is held to what it
+    promises at scale: the draws have the target's moments (65 536 chains x d = 128 standard normal, every dimension within
     2e-3 after 600 draws per chain -- Monte-Carlo error of a variance ~3e-4; d = 200 exercises NS = 4), a chain does not depend
     on how the job is cut into launches or chain blocks, and the parity stream of the same job is untouched by the mode's
     existence."""
