@@ -746,6 +746,31 @@ int lmc_glm_pointwise_loglik(const double* x, int64_t chains, int64_t draws_stri
 #define LMC_PSIS_MAX_TAIL 4096
 int lmc_psis_rows(const double* l, int64_t rows, int64_t S, int64_t row_stride, int32_t tail_len, double* out, void* stream);
 
+/* ---- exact order statistics of the draws in HBM: one pass of a radix select (additive within ABI 9;
+ * littlemcmc_amd/diagnostics.py: order_statistics, quantiles, intervals, tail_ess) ------------------------------------------
+ * The order is the IEEE total order on the bits: for u = the 64 bits of a draw v, its key is
+ *   K(v) = ~u if the sign bit of u is set, else u | 1 << 63      (unsigned compare of keys:
+ *   -NaN < -inf < .. < -0 < +0 < .. < +inf < +NaN; u = K & ~(1 << 63) if bit 63 of K is set, else ~K, gives v back).
+ * x, chains, draws_stride, dim, t0, n, first_chain, chains_per_group: the trace block, sub-series and groups of
+ * lmc_diag_chain_stats_grouped -- the block touches groups g0 .. g1, and a first or last group that lies only partly inside
+ * the block is counted over its chains that are present. shift is one of 56, 48, .., 0; prefix is [g1 - g0 + 1][n_ranks][dim]
+ * keys (DEVICE) and counts is [g1 - g0 + 1][n_ranks][256][dim] (DEVICE, overwritten):
+ *   counts[g][r][b][j] = the number of draws v of dimension j, rows [t0, t0 + n), chains of group g0 + g present in the block,
+ *                        with (K(v) >> shift) & 255 == b and, for shift < 56, K(v) >> (shift + 8) == prefix[g][r][j] >> (shift + 8).
+ * At shift 56 the prefix is not read (it may be NULL) and n_ranks must be 1. The counts are integers and add over chains,
+ * blocks and GPUs exactly: eight passes, after each of which the caller picks per (g, r, j) the bucket where the cumulative
+ * count passes the remaining rank, puts its digit into the prefix and subtracts the count below it, leave the key of the
+ * wanted order statistic. The work is enqueued on `stream` of the current device (a memset of counts, then one kernel);
+ * integer atomics only, so the result does not depend on the order of arrival.
+ * Refused with LMC_ERR_INVALID before any HIP call: NULL x or counts; chains, dim or n < 1; t0 < 0 or t0 + n > draws_stride;
+ * first_chain < 0, chains_per_group < 1; chains, first_chain + chains or n at or beyond 2^31 (a workgroup's 32-bit counters
+ * hold the draws of at least two chains), a result of 2^39 counters or more; a shift that is not a multiple of 8 in 0 .. 56;
+ * n_ranks outside 1 .. LMC_SELECT_MAX_RANKS, or not 1 at shift 56; a NULL prefix below shift 56. */
+#define LMC_SELECT_MAX_RANKS 16
+int lmc_select_digit_counts(const double* x, int64_t chains, int64_t draws_stride, int32_t dim, int64_t t0, int64_t n,
+                            int64_t first_chain, int64_t chains_per_group, int32_t shift, int32_t n_ranks,
+                            const uint64_t* prefix, int64_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

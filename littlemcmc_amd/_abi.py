@@ -21,6 +21,7 @@ TARGET_GLM = 8   # (7 is unassigned) additive within ABI 9: a regression posteri
 GLM_BERNOULLI, GLM_POISSON, GLM_GAUSSIAN = 0, 1, 2
 GLM_MAX_DIM, GLM_HEADER, GLM_MAX_ROW = 512, 8, 1 << 29
 PSIS_MAX_TAIL = 4096   # include/lmc_hip.h: LMC_PSIS_MAX_TAIL, the sorted tail of a row lives in LDS (32 KiB of doubles)
+SELECT_MAX_RANKS = 16   # include/lmc_hip.h: LMC_SELECT_MAX_RANKS, the rank slots of one lmc_select_digit_counts call
 STATUS_BAD_INITIAL_ENERGY = 1
 SDOT_NATIVE, SDOT_OPENBLAS_SKYLAKEX, SDOT_OPENBLAS_HASWELL = 0, 1, 2
 RNG_NUMPY, RNG_PHILOX, RNG_COUNTER = 0, 1, 2
@@ -205,6 +206,8 @@ _SIGNATURES = {
     "lmc_glm_pointwise_loglik": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int64,
                                            C.c_int64, C.c_int64, C.c_int64, C.c_int64, _P, _P]),
     "lmc_psis_rows": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _P, _P]),
+    "lmc_select_digit_counts": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                          C.c_int32, C.c_int32, _P, _P, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

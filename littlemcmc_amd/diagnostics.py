@@ -19,7 +19,11 @@ passes -- ``lmc_diag_chain_stats_grouped``, one launch for all groups and still 
 backend: the HIP kernel. The reduction /
 finalisation logic above it is backend-agnostic tensor code, and the CPU tests of that logic (gloo, world_size 2) inject
 the test oracle's restatement of the kernel's block (oracle/diagnostics_oracle.py: torch_chain_stats) through the
-``stats_fn`` argument; nothing in this package computes the statistics on the host."""
+``stats_fn`` argument; nothing in this package computes the statistics on the host.
+
+Posterior quantiles, equal-tailed credible intervals and tail-ESS (``order_statistics``, ``quantiles``, ``intervals``,
+``tail_ess``, at the end of this module) follow the same rule with an integer statistic: a radix select whose passes are
+histograms of key digits from ``lmc_select_digit_counts`` (csrc/lmc_select.hip), exact and additive over chains and GPUs."""
 import ctypes
 import math
 
@@ -493,3 +497,223 @@ def trace_tensor(engine, n_draws=None):
     engine.synchronize()
     shape = (engine.chains, engine.trace_rows(), engine.dim)
     return torch.as_tensor(_DevicePtr(ptr, shape), device="cuda:%d" % engine.cfg.device)
+
+
+# ---- exact order statistics of the trace in place: posterior quantiles, credible intervals, tail-ESS ---------------------
+# A radix select over the order-preserving 64-bit keys of the draws (include/lmc_hip.h: lmc_select_digit_counts). A pass is
+# an INTEGER HISTOGRAM of one key digit, which adds over chains, chain blocks and GPUs exactly, so a posterior spread over
+# several devices is no special case; eight passes leave the key of the wanted draw, bit for bit. Keys and prefixes travel
+# as int64 tensors holding the unsigned bits.
+SELECT_SHIFTS = (56, 48, 40, 32, 24, 16, 8, 0)
+_INT64_MIN = -(1 << 63)
+
+
+def _hip_select_counts(x, first_chain, per, shift, prefix):
+    """One call of lmc_select_digit_counts over x[chains, draws, d] (a ROCm tensor): -> [groups touched, n_ranks, 256, d] int64
+    on x's device. ``prefix`` is [groups touched, n_ranks, d] int64 on that device (None at shift 56: one rank slot)."""
+    from . import _abi
+
+    lib = _abi.load()
+    x = _device_block(x)
+    c, n, d = x.shape
+    stride = x.stride(0) // d if c > 1 else n
+    touched = _touched(first_chain, c, per)[1]
+    n_ranks = 1 if prefix is None else int(prefix.shape[1])
+    if prefix is not None:
+        prefix = prefix.contiguous()
+        if tuple(prefix.shape) != (touched, n_ranks, d) or prefix.dtype != torch.int64 or prefix.device != x.device:
+            raise ValueError("prefix must be int64 [%d, n_ranks, %d] on %s" % (touched, d, x.device))
+    out = torch.empty((touched, n_ranks, 256, d), dtype=torch.int64, device=x.device)
+    with torch.cuda.device(x.device):
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        rc = lib.lmc_select_digit_counts(ctypes.c_void_p(x.data_ptr()), c, stride, d, 0, n, int(first_chain), int(per), int(shift),
+                                         n_ranks, ctypes.c_void_p(prefix.data_ptr()) if prefix is not None else None,
+                                         ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(stream))
+    if rc != 0:
+        raise RuntimeError("lmc_select_digit_counts failed (status %d)" % rc)
+    return out
+
+
+def _select_job(x, chains_per_group):
+    """(blocks that hold chains, their first job chains, per, G, n, d) of an order-statistics job; refusals."""
+    blocks = _blocks(x)
+    if not blocks:
+        raise ValueError("no chain block")
+    if _group_active():
+        raise ValueError("quantiles with an active process group: order statistics are taken within one process (pass the "
+                         "list of its per-GPU blocks), not reduced across ranks")
+    if any(b.dim() != 3 for b in blocks):
+        raise ValueError("draws must be [chains, draws, d]")
+    if len({int(b.shape[2]) for b in blocks}) > 1:
+        raise ValueError("the chain blocks differ in d: %s" % [int(b.shape[2]) for b in blocks])
+    firsts, held = [], []
+    c = 0
+    for b in blocks:
+        if b.shape[0] > 0:
+            firsts.append(c)
+            held.append(b)
+        c += int(b.shape[0])
+    if len({int(b.shape[1]) for b in held}) > 1:
+        raise ValueError("the chain blocks hold different numbers of draws per chain: %s" % [int(b.shape[1]) for b in held])
+    if not held or held[0].shape[1] < 1 or held[0].shape[2] < 1:
+        raise ValueError("no draws: x is empty")
+    per = c if chains_per_group is None else _chains_per_group(c, chains_per_group)
+    return held, firsts, per, c // per, int(held[0].shape[1]), int(held[0].shape[2])
+
+
+def _select_counts(held, firsts, per, ga, gb, shift, prefix, count_fn, dev):
+    """Digit counts [gb - ga, n_ranks, 256, d] of the groups [ga, gb) of the job, on ``dev``: every block counts the part of
+    those groups' chains it holds, on its own device (all enqueued before the first result moves), and the parts are added."""
+    fn = _hip_select_counts if count_fn is None else count_fn
+    parts = []
+    for b, f in zip(held, firsts):
+        lo, hi = max(ga * per, f), min(gb * per, f + int(b.shape[0]))
+        if lo >= hi:
+            continue
+        off, touched = _touched(lo, hi - lo, per)
+        pf = None if prefix is None else prefix[off - ga:off - ga + touched].to(b.device)
+        parts.append((off - ga, fn(b[lo - f:hi - f], lo, per, shift, pf)))
+    tot = None
+    for off, p_ in parts:
+        if tot is None and off == 0 and p_.shape[0] == gb - ga:
+            tot = p_.to(dev)
+            continue
+        if tot is None:
+            tot = torch.zeros((gb - ga,) + tuple(p_.shape[1:]), dtype=torch.int64, device=dev)
+        tot[off:off + p_.shape[0]] += p_.to(dev)
+    return tot
+
+
+def order_statistics(x, ranks, chains_per_group=None, scratch_bytes=1 << 30, count_fn=None):
+    """Exact order statistics of the draws in HBM: entry k of the result [Q', d] float64 (with ``chains_per_group=per``:
+    [G, Q', d], one posterior per ``per`` consecutive chains) is the ``ranks[k]``-th smallest (0-based) of the S = chains of a
+    group x draws values of that dimension -- the draw itself, bit for bit. The order is the IEEE total order on the bits
+    (-NaN < -inf < .. < -0 < +0 < .. < +inf < +NaN).
+
+    x is one tensor [chains, draws, d], or the list of per-GPU blocks of one job (``trace_tensor(engine_group)``): every block
+    is counted on its own device at its running first chain, the integer counts are added on the first block's device, and a
+    group -- or the whole ungrouped job -- may straddle blocks. Eight passes over the trace (lmc_select_digit_counts, 8 key
+    bits each, most significant first): after each, per (group, rank, dimension), the bucket where the cumulative count passes
+    the remaining rank extends the prefix and the count below it is subtracted. Duplicated ranks are selected once; more than
+    16 distinct ranks take several rounds of passes that share the first (shift 56) pass. The groups are taken in chunks so
+    that the counts of a pass ([groups, ranks of the round, 256, d] int64) stay within ``scratch_bytes``; ValueError if one
+    group alone does not fit. Nothing in the pass loop looks at the host. ``count_fn(x, first_chain, per, shift, prefix) ->
+    counts`` replaces the HIP call (tests of this logic only); without it a CPU tensor raises HipLibraryError. Not with an
+    active process group."""
+    from . import _abi
+
+    held, firsts, per, G, n, d = _select_job(x, chains_per_group)
+    S = per * n
+    want = [int(r) for r in ranks]
+    if not want:
+        raise ValueError("no ranks")
+    if min(want) < 0 or max(want) >= S:
+        raise ValueError("ranks must lie in [0, %d) (got %d .. %d)" % (S, min(want), max(want)))
+    uniq = sorted(set(want))
+    rounds = [uniq[i:i + _abi.SELECT_MAX_RANKS] for i in range(0, len(uniq), _abi.SELECT_MAX_RANKS)]
+    unit = 256 * d * 8 * max(len(r) for r in rounds)
+    chunk = int(scratch_bytes) // unit
+    if chunk < 1:
+        raise ValueError("scratch_bytes=%d is below the %d bytes of one group's counts (%d ranks x 256 x %d dimensions x 8)"
+                         % (scratch_bytes, unit, max(len(r) for r in rounds), d))
+    dev = held[0].device
+    if count_fn is None:
+        for b in held:
+            _device_block(b)     # HipLibraryError for a CPU tensor: there is no host implementation
+    out = torch.empty((G, len(uniq), d), dtype=torch.float64, device=dev)
+    for ga in range(0, G, chunk):
+        gb = min(ga + chunk, G)
+        # the shift-56 pass is shared by the rounds; the cumulative counts overwrite the counts (no second table)
+        first = _select_counts(held, firsts, per, ga, gb, SELECT_SHIFTS[0], None, count_fn, dev).cumsum_(2)
+        q0 = 0
+        for rks in rounds:
+            rem = torch.tensor(rks, dtype=torch.int64, device=dev).reshape(1, -1, 1).expand(gb - ga, len(rks), d).contiguous()
+            prefix = torch.zeros((gb - ga, len(rks), d), dtype=torch.int64, device=dev)
+            for shift in SELECT_SHIFTS:
+                if shift == SELECT_SHIFTS[0]:
+                    cum = first.expand(-1, len(rks), -1, -1)                      # [g, ranks, 256, d]
+                else:
+                    cum = _select_counts(held, firsts, per, ga, gb, shift, prefix, count_fn, dev).cumsum_(2)
+                bucket = (cum <= rem.unsqueeze(2)).sum(dim=2).clamp_(max=255)     # the first bucket whose cumulative count passes
+                below = torch.gather(cum, 2, (bucket - 1).clamp_(min=0).unsqueeze(2)).squeeze(2)
+                rem = rem - torch.where(bucket > 0, below, torch.zeros_like(below))
+                prefix = prefix | (bucket << shift)
+            bits = torch.where(prefix < 0, prefix ^ _INT64_MIN, ~prefix)          # the key back to the draw's bits
+            out[ga:gb, q0:q0 + len(rks)] = bits.view(torch.float64)
+            q0 += len(rks)
+    pick = torch.tensor([uniq.index(r) for r in want], dtype=torch.int64, device=dev)
+    out = out.index_select(1, pick)
+    return out if chains_per_group is not None else out[0]
+
+
+def quantiles(x, probs, chains_per_group=None, **kw):
+    """Posterior quantiles from the trace in place -> dict(quantiles[Q, d], min[d], max[d], n, probs); with
+    ``chains_per_group=per`` quantiles[G, Q, d], min[G, d], max[G, d]. With v the sorted S = chains x draws values of a
+    (group, dimension), by linear interpolation between order statistics (numpy's default):
+
+        h = p (S - 1),  lo = floor(h),  q = v[lo] + (v[min(lo + 1, S - 1)] - v[lo]) (h - lo)
+
+    v[lo] and v[lo + 1] are exact (``order_statistics``; ``**kw`` goes there); ``min`` and ``max`` are ranks 0 and S - 1,
+    always selected; ``n`` is S. A (group, dimension) whose min or max is NaN holds a NaN draw and all its quantiles are
+    NaN, as numpy's are. ``probs`` must lie in [0, 1] and must not be empty."""
+    probs = [float(p) for p in (probs.tolist() if hasattr(probs, "tolist") else probs)]
+    if not probs or any(not (0.0 <= p <= 1.0) for p in probs):
+        raise ValueError("probs must be a non-empty sequence of numbers in [0, 1] (got %r)" % (probs,))
+    held, _firsts, per, _G, n, _d = _select_job(x, chains_per_group)
+    S = per * n
+    h = [p * (S - 1) for p in probs]
+    lo = [int(math.floor(v)) for v in h]
+    hi = [min(k + 1, S - 1) for k in lo]
+    os_ = order_statistics(x, [0, S - 1] + lo + hi, chains_per_group=chains_per_group, **kw)
+    Q = len(probs)
+    vmin, vmax = os_[..., 0, :], os_[..., 1, :]
+    vlo, vhi = os_[..., 2:2 + Q, :], os_[..., 2 + Q:, :]
+    frac = torch.tensor([a - b for a, b in zip(h, lo)], dtype=torch.float64, device=os_.device).reshape(Q, 1)
+    q = vlo + (vhi - vlo) * frac
+    bad = (torch.isnan(vmin) | torch.isnan(vmax)).unsqueeze(-2)
+    q = torch.where(bad, torch.full_like(q, float("nan")), q)
+    return {"quantiles": q, "min": vmin, "max": vmax, "n": S, "probs": probs}
+
+
+def intervals(x, level=0.9, chains_per_group=None, **kw):
+    """Equal-tailed credible intervals -> dict(lower, median, upper, level): the quantiles at (1 - level) / 2, 1 / 2 and
+    1 - (1 - level) / 2 of ``quantiles`` ([d] each, [G, d] with ``chains_per_group``). Highest-density intervals are not
+    computed."""
+    level = float(level)
+    if not (0.0 < level < 1.0):
+        raise ValueError("level must lie in (0, 1) (got %r)" % (level,))
+    tail = (1.0 - level) / 2.0
+    q = quantiles(x, [tail, 0.5, 1.0 - tail], chains_per_group=chains_per_group, **kw)["quantiles"]
+    return {"lower": q[..., 0, :], "median": q[..., 1, :], "upper": q[..., 2, :], "level": level}
+
+
+def tail_ess(x, probs=(0.05, 0.95), split=True, chains_per_group=None, chunk_dims=8, stats_fn=None, **kw):
+    """Tail effective sample size (Vehtari et al. 2021): the minimum over ``probs`` of the (split) ESS of the indicator
+    x <= q_p, q_p the posterior quantile of ``quantiles`` -> dict(ess_tail[d]); ess_tail[G, d] and ess_tail_min[G] with
+    ``chains_per_group``. The indicator is built for ``chunk_dims`` dimensions at a time -- the temporary is chains x draws x
+    chunk_dims doubles, the bound rank_normalize keeps -- and goes through ``sufficient_stats`` / ``finalize`` like any draws.
+    ``**kw`` goes to ``order_statistics``; ``stats_fn`` to ``sufficient_stats``."""
+    q = quantiles(x, probs, chains_per_group=chains_per_group, **kw)["quantiles"]
+    held, firsts, per, G, n, d = _select_job(x, chains_per_group)
+    best = None
+    for k in range(q.shape[-2]):
+        parts = []
+        for lo in range(0, d, int(chunk_dims)):
+            hi = min(lo + int(chunk_dims), d)
+            ind = []
+            for b, f in zip(held, firsts):
+                qk = q[..., k, lo:hi].to(b.device)
+                if chains_per_group is not None:   # the quantile of every chain's own group
+                    rows = (torch.arange(int(b.shape[0]), device=b.device) + f) // per
+                    qk = qk.index_select(0, rows)
+                    ind.append((b[:, :, lo:hi] <= qk.unsqueeze(1)).to(torch.float64))
+                else:
+                    ind.append((b[:, :, lo:hi] <= qk).to(torch.float64))
+            st = sufficient_stats(ind if len(ind) > 1 else ind[0], split=split, stats_fn=stats_fn, chains_per_group=chains_per_group)
+            parts.append(finalize(st)["ess"].to(q.device))
+        ess = torch.cat(parts, dim=-1)
+        best = ess if best is None else torch.minimum(best, ess)
+    out = {"ess_tail": best, "probs": [float(p) for p in probs]}
+    if chains_per_group is not None:
+        out.update(groups=G, ess_tail_min=best.min(dim=-1).values)
+    return out

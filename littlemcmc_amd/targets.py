@@ -713,6 +713,28 @@ class Batched(DeviceTarget):
         chains = sum(int(b.shape[0]) for b in x) if isinstance(x, (list, tuple)) else int(x.shape[0])
         return diagnostics.summarize(x, chains_per_group=self.group_size(chains), **kw)
 
+    def _per(self, x):
+        return self.group_size(sum(int(b.shape[0]) for b in x) if isinstance(x, (list, tuple)) else int(x.shape[0]))
+
+    def quantiles(self, x, probs, **kw):
+        """``diagnostics.quantiles`` per posterior: exact quantiles[G, Q, d], min[G, d], max[G, d] from the draws in HBM (one
+        tensor or the list of per-GPU blocks)."""
+        from . import diagnostics
+
+        return diagnostics.quantiles(x, probs, chains_per_group=self._per(x), **kw)
+
+    def intervals(self, x, level=0.9, **kw):
+        """``diagnostics.intervals`` per posterior: equal-tailed lower[G, d], median[G, d], upper[G, d]."""
+        from . import diagnostics
+
+        return diagnostics.intervals(x, level, chains_per_group=self._per(x), **kw)
+
+    def tail_ess(self, x, **kw):
+        """``diagnostics.tail_ess`` per posterior: ess_tail[G, d], ess_tail_min[G]."""
+        from . import diagnostics
+
+        return diagnostics.tail_ess(x, chains_per_group=self._per(x), **kw)
+
     def pointwise_stats(self, x, **kw):
         """``predictive.pointwise_stats(x, self, ...)`` per posterior (GLM members): the per-observation statistics ``[G, N]``."""
         from . import predictive
