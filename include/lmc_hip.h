@@ -771,6 +771,39 @@ int lmc_select_digit_counts(const double* x, int64_t chains, int64_t draws_strid
                             int64_t first_chain, int64_t chains_per_group, int32_t shift, int32_t n_ranks,
                             const uint64_t* prefix, int64_t* counts, void* stream);
 
+/* ---- posterior predictions at new X, GLM family (additive within ABI 9; littlemcmc_amd/predictive.py: linear_predictor,
+ * predict) ----------------------------------------------------------------------------------------------------------------
+ * x .. chains_per_group are the arguments of lmc_glm_pointwise. rows are GLM parameter rows of the POINTS TO PREDICT AT (the
+ * LMC_TARGET_GLM layout at the posterior's dim: the training design, or a design whose response is unknown); their y section
+ * is NOT READ. [ob0, ob1) are blocks of 64 observations as in lmc_glm_pointwise_loglik; W = (ob1 - ob0) * 64. With
+ * eta[s, i] = sum_e X[i][e] q_s[e] the linear predictor of draw s at observation i -- e ascending, one fma per term: the eta of
+ * the sampler and of lmc_glm_pointwise, bit for bit (one device function) -- the call has two outputs, either of which may be
+ * NULL, not both:
+ *   eta    [chains][n][W] doubles (DEVICE): eta[c][t][64 (ob - ob0) + lane] is the linear predictor of draw t0 + t of chain c
+ *          of the block at observation 64 ob + lane. This is the [chains, draws, dim] layout of a trace with dim = W and
+ *          draws_stride = n, which lmc_select_digit_counts and lmc_diag_chain_stats_grouped read: the exact order statistics
+ *          of the predictor are those calls on this array, with the same first_chain and chains_per_group. Whole groups are
+ *          not demanded (a chain's rows are its own).
+ *   stats  [g1 - g0 + 1][5][W] doubles (DEVICE), the block touching groups g0 .. g1: per group and observation, over the n_g
+ *          draws of the group that lie in x, rows [t0, t0 + n):
+ *            [0] n_g (as a double)   [1] mean_s eta   [2] M2 = sum_s (eta - mean)^2   [3] mean_s mu   [4] sum_s (mu - mean mu)^2
+ *          mu the mean response: sigmoid(eta) (bernoulli), exp(eta) (poisson), eta (gaussian). Two blocks a, b of draws merge
+ *          by Chan's update, mean = mean_a + (mean_b - mean_a) nb / n, M2 = M2a + M2b + (mean_b - mean_a)^2 na nb / n, a block
+ *          of count 0 skipped by its count; a group that lies only partly in x gets the block of its draws that are present.
+ * Observations i >= N (padding up to npad) hold eta = 0. Bit-reproducible: no floating-point atomics; the statistics are
+ * two-pass per tile of 8 draws, merged per chain in draw order and then per group in (chain, 256-draw segment) order, a plan
+ * that depends on the shape alone -- so two calls, a call on a sub-range of observation blocks and a call without the other
+ * output all give the same bits. A non-finite eta or mu (a NaN or infinite coefficient, an overflowing poisson exp(eta))
+ * makes the planes [1] .. [4] it enters of THAT (group, observation) non-finite (+-inf or NaN) and touches nothing else; the
+ * mu of a NaN eta is NaN, so a NaN coefficient makes all four planes of its group NaN at every observation.
+ * Refused with LMC_ERR_INVALID before any HIP call: what lmc_glm_pointwise refuses before its header copy (its `out` aside);
+ * ob0 < 0, ob1 <= ob0, ob1 > npad / 64; eta and stats both NULL; chains * n * W >= 2^40 elements of eta (the kernels index
+ * with 64 bits; the launch is the limit:) chains * ceil(n / 256) * (ob1 - ob0) >= 2^31. Then the header check of
+ * lmc_glm_pointwise, on the touched rows. */
+int lmc_glm_linpred(const double* x, int64_t chains, int64_t draws_stride, int32_t dim, int64_t t0, int64_t n,
+                    const double* rows, int64_t row_len, int64_t n_rows, int64_t first_chain, int64_t chains_per_group,
+                    int64_t ob0, int64_t ob1, double* eta, double* stats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -208,6 +208,8 @@ _SIGNATURES = {
     "lmc_psis_rows": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _P, _P]),
     "lmc_select_digit_counts": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
                                           C.c_int32, C.c_int32, _P, _P, _P]),
+    "lmc_glm_linpred": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int64,
+                                  C.c_int64, C.c_int64, C.c_int64, _P, _P, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

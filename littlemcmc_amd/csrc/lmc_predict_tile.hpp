@@ -1,6 +1,7 @@
 // The eta / link tile of the pointwise predictive kernels, stated ONCE: pointwise_kernel (lmc_predict.hip) reduces the
 // l[], mu[] it returns to the six planes, pointwise_loglik_kernel (lmc_psis.hip) writes the same l[] out -- the same
-// instructions on the same operands, so the written array holds the bits the planes were reduced from.
+// instructions on the same operands, so the written array holds the bits the planes were reduced from. The contraction
+// alone is glm_eta_tile, which linpred_kernel (lmc_linpred.hip) writes out: the eta of a prediction is the eta of the score.
 //
 // One wavefront, lane = observation (the Xt[e][n] section of the GLM row: one coalesced 512-byte row per coefficient and
 // block of 64 observations). A tile is kPredT consecutive draws of one chain: the trace row q is read through a wave-uniform
@@ -26,15 +27,15 @@ __device__ __forceinline__ double grow_at(GRow base, unsigned bytes) {
     return *reinterpret_cast<GRow>(reinterpret_cast<const __attribute__((address_space(1))) char*>(base) + bytes);
 }
 
-// qt: the tile's first draw (dim doubles a draw), k <= kPredT draws of it exist (wave-uniform); xt: the row's Xt section,
-// col0 the lane's byte offset in a row of it, row_bytes = npad * 8; yn the lane's y. l[i], mu[i] for i >= k repeat draw k - 1.
-__device__ __forceinline__ void glm_link_tile(const double* qt, int k, int dim, GRow xt, unsigned col0, unsigned row_bytes,
-                                              int lik, double yn, double isig2, double (&l)[kPredT], double (&mu)[kPredT]) {
+// The contraction alone: eta[i] of the tile's draws. qt: the tile's first draw (dim doubles a draw), k <= kPredT draws of it
+// exist (wave-uniform); xt: the row's Xt section, col0 the lane's byte offset in a row of it, row_bytes = npad * 8. eta[i] for
+// i >= k repeats draw k - 1. The y section of the row is not touched (lmc_linpred.hip predicts where no y is known).
+__device__ __forceinline__ void glm_eta_tile(const double* qt, int k, int dim, GRow xt, unsigned col0, unsigned row_bytes,
+                                             double (&eta)[kPredT]) {
     // a tile's missing draws repeat its last one (a valid row; the callers deselect their values)
     int qoff[kPredT];
 #pragma unroll
     for (int i = 0; i < kPredT; ++i) qoff[i] = (i < k ? i : k - 1) * dim;
-    double eta[kPredT];
 #pragma unroll
     for (int i = 0; i < kPredT; ++i) eta[i] = 0.0;
     unsigned col = col0;
@@ -64,7 +65,12 @@ __device__ __forceinline__ void glm_link_tile(const double* qt, int k, int dim, 
             }
         }
     }
-    // ---- link: the functor's expressions
+}
+
+// The link of a tile's eta, the functor's expressions: l[i] the pointwise log-likelihood at the lane's y = yn (constants
+// dropped), mu[i] the mean response sigmoid(eta) | exp(eta) | eta. A caller that wants mu alone passes any yn and drops l.
+__device__ __forceinline__ void glm_link_of_eta(int lik, double yn, double isig2, const double (&eta)[kPredT],
+                                                double (&l)[kPredT], double (&mu)[kPredT]) {
     if (lik == kGlmBernoulli) {
 #pragma unroll
         for (int i = 0; i < kPredT; ++i) {
@@ -86,6 +92,14 @@ __device__ __forceinline__ void glm_link_tile(const double* qt, int k, int dim, 
             l[i] = -0.5 * ((res * res) * isig2);
         }
     }
+}
+
+// eta and the link of a tile: yn the lane's y. l[i], mu[i] for i >= k repeat draw k - 1.
+__device__ __forceinline__ void glm_link_tile(const double* qt, int k, int dim, GRow xt, unsigned col0, unsigned row_bytes,
+                                              int lik, double yn, double isig2, double (&l)[kPredT], double (&mu)[kPredT]) {
+    double eta[kPredT];
+    glm_eta_tile(qt, k, dim, xt, col0, row_bytes, eta);
+    glm_link_of_eta(lik, yn, isig2, eta, l, mu);
 }
 
 // npad of a GLM row of row_len doubles at dimension dim, or 0 if no N gives that length (pure arithmetic)

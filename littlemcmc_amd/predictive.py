@@ -9,7 +9,10 @@ They come from one streaming pass of the HIP kernel ``lmc_glm_pointwise`` (csrc/
 ``l`` itself -- N / d times the size of the trace -- is never written. ``l`` is the device functor's ``l_n`` (``targets.GLM``:
 constants that do not depend on the coefficients dropped); :func:`finalize` adds ``GLM.loglik_constant()`` back. There is
 one backend, the HIP kernel; the merge / finalise logic above it is plain tensor code, and its CPU tests inject a numpy
-restatement of the kernel's block through ``stats_fn`` (as ``diagnostics.summarize`` does)."""
+restatement of the kernel's block through ``stats_fn`` (as ``diagnostics.summarize`` does).
+
+Further down: PSIS-LOO (``psis``, ``loo``; csrc/lmc_psis.hip) and posterior predictions at new X (``linear_predictor``,
+``predict``; csrc/lmc_linpred.hip), each with its own kernel and its own injected model in the CPU tests."""
 import ctypes
 import weakref
 
@@ -450,3 +453,248 @@ def loo(x, target, reff=1.0, scratch_bytes=1 << 30, psis_fn=None, loglik_fn=None
     out["looic"] = -2.0 * out["elpd_loo"]
     out["n_bad_k"] = (out["pareto_k"] > BAD_K).sum(dim=-1)
     return out
+
+
+# ---- posterior predictions at new X (csrc/lmc_linpred.hip; include/lmc_hip.h: lmc_glm_linpred) ------------------------------
+MOMENT_PLANES = ("n", "eta_mean", "eta_M2", "mu_mean", "mu_M2")
+
+
+def merge_moments(a, b):
+    """Two blocks ``[..., 5, W]`` of the planes ``n, mean eta, M2 eta, mean mu, M2 mu`` over disjoint sets of draws -> the
+    block over their union: Chan's update of both (mean, M2) pairs, the rule of :func:`merge`. A side of count 0 is skipped
+    BY ITS COUNT: the other side comes through bit for bit, whatever the empty side holds."""
+    na, mea, M2a, mma, N2a = a.unbind(-2)
+    nb, meb, M2b, mmb, N2b = b.unbind(-2)
+    n = na + nb
+    safe = torch.where(n > 0, n, torch.ones_like(n))
+    w, cross = nb / safe, na * nb / safe
+    de, dm = meb - mea, mmb - mma
+    both = torch.stack([n, mea + de * w, (M2a + M2b) + (de * de) * cross, mma + dm * w, (N2a + N2b) + (dm * dm) * cross], dim=-2)
+    only_a, only_b = (nb == 0).unsqueeze(-2), (na == 0).unsqueeze(-2)
+    return torch.where(only_a, a, torch.where(only_b, b, both))
+
+
+def _predicted(target, members, X_new):
+    """(table[G, row_len] (host), N_new) of the points to predict at: the training design, or ``X_new`` validated as
+    :func:`_scored` validates ``data=`` -- through ``GLM(X_new, zeros, ...)`` of the member's likelihood and scales (the y
+    section of such a row is never read)."""
+    from .targets import GLM, Batched
+
+    if X_new is None:
+        return np.ascontiguousarray(target.params, dtype=np.float64).reshape(len(members), -1), members[0].n_obs
+    if isinstance(target, Batched):
+        designs = list(X_new)
+        if len(designs) != len(members):
+            raise ValueError("X_new for a Batched of %d groups is a list of %d arrays [N_new, d] (got %d)"
+                             % (len(members), len(members), len(designs)))
+    else:
+        designs = [X_new]
+    held = []
+    for g, (m, X) in enumerate(zip(members, designs)):
+        X = np.asarray(X, dtype=np.float64)
+        if X.ndim != 2:
+            raise ValueError("X_new of group %d must be [N_new, d] (got shape %r)" % (g, tuple(X.shape)))
+        if X.shape[1] != m.d:
+            raise ValueError("X_new of group %d has d = %d, the posterior d = %d" % (g, X.shape[1], m.d))
+        if held and X.shape[0] != held[0].n_obs:
+            raise ValueError("X_new of group %d has N_new = %d, group 0 N_new = %d: one common N_new" % (g, X.shape[0], held[0].n_obs))
+        held.append(GLM(X, np.zeros(X.shape[0]), likelihood=m.likelihood, prior_scale=m.prior_scale, sigma=m.sigma))
+    return np.stack([h.params for h in held]), held[0].n_obs
+
+
+def _hip_linpred(x, table, first_chain, per, ob0, ob1, want_eta=True, want_stats=True):
+    """One call of lmc_glm_linpred: x[chains, draws, d] (float64, _row_major, on a ROCm device), table[n_rows, row_len] on the
+    same device -> (eta[chains, draws, W] or None, stats[groups touched, 5, W] or None), W = 64 (ob1 - ob0)."""
+    from . import _abi
+
+    lib = _abi.load()
+    c, n, d = x.shape
+    stride = x.stride(0) // d if c > 1 else n
+    n_rows, row_len = table.shape
+    W = 64 * (int(ob1) - int(ob0))
+    eta = torch.empty((c, n, W), dtype=torch.float64, device=x.device) if want_eta else None
+    stats = (torch.empty((diagnostics._touched(first_chain, c, per)[1], len(MOMENT_PLANES), W), dtype=torch.float64, device=x.device)
+             if want_stats else None)
+    with torch.cuda.device(x.device):
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        rc = lib.lmc_glm_linpred(ctypes.c_void_p(x.data_ptr()), c, stride, d, 0, n, ctypes.c_void_p(table.data_ptr()), row_len,
+                                 n_rows, int(first_chain), int(per), int(ob0), int(ob1),
+                                 ctypes.c_void_p(eta.data_ptr()) if want_eta else None,
+                                 ctypes.c_void_p(stats.data_ptr()) if want_stats else None, ctypes.c_void_p(stream))
+    if rc != 0:
+        raise RuntimeError("lmc_glm_linpred failed (status %d)" % rc)
+    return eta, stats
+
+
+def _linpred_block(b, target, table, cache, first, per, ob0, ob1, linpred_fn, want_eta=True, want_stats=True):
+    """``cache``: the table is the target's own (kept on the device with the target) or a dict device -> table of this call."""
+    if linpred_fn is not None:
+        return linpred_fn(b, table, first, per, ob0, ob1, want_eta, want_stats)
+    b = diagnostics._device_block(b)
+    if cache is True:
+        tab = _table_on(target, table, b.device, True)
+    else:
+        key = str(b.device)
+        if key not in cache:
+            cache[key] = torch.as_tensor(table).to(b.device)
+        tab = cache[key]
+    return _hip_linpred(b, tab, first, per, ob0, ob1, want_eta, want_stats)
+
+
+def _predict_plan(x, target, chains_per_group):
+    """The blocks of a prediction job: (members, blocks that hold chains, their first job chains, per, n_draws)."""
+    from .targets import Batched
+
+    members = _members(target)
+    if diagnostics._group_active(None):
+        raise ValueError("posterior predictions are a one-process matter: an active process group (sample_distributed) is not "
+                         "supported")
+    blocks = list(x) if isinstance(x, (list, tuple)) else [x]
+    if not blocks or any(b.dim() != 3 for b in blocks):
+        raise ValueError("x must be [chains, draws, d] or a list of such blocks")
+    held, firsts, f = [], [], 0
+    for b in blocks:
+        if b.shape[0] > 0:
+            held.append(b)
+            firsts.append(f)
+        f += int(b.shape[0])
+    if not held:
+        raise ValueError("x holds no chain")
+    if len({(int(b.shape[1]), int(b.shape[2])) for b in held}) > 1:
+        raise ValueError("the chain blocks differ in draws per chain or in d: %s" % [tuple(b.shape[1:]) for b in held])
+    n_draws, d = int(held[0].shape[1]), int(held[0].shape[2])
+    if d != members[0].d:
+        raise ValueError("x has d = %d, the target d = %d" % (d, members[0].d))
+    if n_draws < 1:
+        raise ValueError("x holds no draw")
+    if chains_per_group is None:
+        per = target.group_size(f) if isinstance(target, Batched) else f
+    else:
+        per = int(chains_per_group)
+    if per < 1 or per * len(members) != f:
+        raise ValueError("%d chains at %d chains per group are not the %d posteriors of the target" % (f, per, len(members)))
+    return members, held, firsts, per, n_draws
+
+
+def linear_predictor(x, target, X_new=None, obs_blocks=None, linpred_fn=None):
+    """The linear predictor itself and its moments, from ONE tensor of draws ``x[chains, draws, d]`` (the whole job of
+    ``target``) -> ``(eta[chains, draws, W], stats)``: ``eta[c, t, i]`` is ``X_new[64 * ob0 + i] @ x[c, t]`` on the row of
+    chain c's group -- the sampler's own contraction, bit for bit; observations beyond N_new are padding (0) -- and ``stats``
+    is a dict of ``[G, W]`` tensors ``n, eta_mean, eta_M2, mu_mean, mu_M2`` (``MOMENT_PLANES``). It is N_new / d times the
+    trace: meant for tests and small jobs, :func:`predict` walks it in chunks. ``X_new=None`` means the training design;
+    ``obs_blocks=(ob0, ob1)`` selects a half-open range of blocks of 64 observations (default: all). ``linpred_fn(x, table,
+    first_chain, per, ob0, ob1, want_eta, want_stats) -> (eta, stats[groups touched, 5, W])`` replaces the HIP call."""
+    if isinstance(x, (list, tuple)):
+        raise ValueError("linear_predictor takes one tensor; predict() takes the list of per-GPU blocks of a job")
+    members, held, firsts, per, _n = _predict_plan(x, target, None)
+    table, n_new = _predicted(target, members, X_new)
+    nob = (n_new + 63) // 64
+    ob0, ob1 = (0, nob) if obs_blocks is None else (int(obs_blocks[0]), int(obs_blocks[1]))
+    if not (0 <= ob0 < ob1 <= nob):
+        raise ValueError("obs_blocks=%r of %d: a half-open, non-empty range" % (obs_blocks, nob))
+    eta, st = _linpred_block(held[0], target, table, True if X_new is None else {}, 0, per, ob0, ob1, linpred_fn)
+    return eta, {name: st[:, i] for i, name in enumerate(MOMENT_PLANES)}
+
+
+def _inverse_link(likelihood, eta):
+    return {"bernoulli": torch.sigmoid, "poisson": torch.exp, "gaussian": lambda v: v}[likelihood](eta)
+
+
+def predict(x, target, X_new=None, probs=(0.05, 0.5, 0.95), chains_per_group=None, scratch_bytes=1 << 30, linpred_fn=None,
+            count_fn=None):
+    """Posterior predictions of a ``GLM`` (leading axis 1) or of every posterior of a ``Batched`` of GLMs (leading axis G) at
+    the points ``X_new`` -- ``[N_new, d]``, for a ``Batched`` a list of G such arrays with one common N_new; ``None``: the
+    training design -- from the draws in HBM. A dict of float64 tensors on x's device:
+
+    ``eta_mean, eta_sd, mu_mean, mu_sd`` ``[G, N_new]``: the posterior mean and standard deviation ``sqrt(M2 / (n - 1))`` (NaN
+    for one draw) of the linear predictor ``eta = x'q`` and of the mean response ``mu = sigmoid(eta) | exp(eta) | eta``
+    (bernoulli | poisson | gaussian), from the kernel's merged moments;
+    ``eta_quantiles`` ``[G, Q, N_new]``: the quantiles at ``probs`` of eta, as ``diagnostics.quantiles`` gives them for a trace:
+    EXACT order statistics of the written eta (the radix select) and numpy's linear interpolation;
+    ``mu_quantiles`` ``[G, Q, N_new]``: the credible band of the mean response. The inverse link is monotone, so THE SORTED mu
+    ARE DEFINED AS the inverse link (``torch.sigmoid``, ``torch.exp``, the identity; on the host) of the sorted eta: the link
+    is applied to the two neighbouring eta order statistics of each probability and the interpolation is done on the mu
+    scale -- no second select;
+    ``y_mean, y_var`` ``[G, N_new]``: the posterior-predictive mean and variance of a NEW response by the law of total
+    variance, without simulation -- bernoulli: ``mu_mean``, ``mu_mean (1 - mu_mean)``; poisson: ``mu_mean``,
+    ``mu_mean + var mu``; gaussian: ``eta_mean``, ``sigma^2 + var eta`` (var = M2 / (n - 1));
+    ``n``: S = chains of a group x draws, the draws per posterior; ``probs``.
+
+    ``x`` is one tensor ``[chains, draws, d]`` or the list of per-GPU blocks of the job: each block runs on its own device at
+    its running first chain (a group may straddle blocks), the moments merge on the first block's device
+    (:func:`merge_moments`) and the select adds its integer counts across blocks. The linear predictor is written
+    (``lmc_glm_linpred``) in chunks of blocks of 64 observations: the chunks of a pass (``chains x draws x 64 x 8`` bytes an
+    observation block, over all devices) plus the select's counts stay within ``scratch_bytes`` -- the select gets the rest
+    through its own ``scratch_bytes=`` -- and ValueError if one observation block does not fit. Columns are independent, so the
+    chunking does not change a bit. ``linpred_fn`` (see :func:`linear_predictor`) and ``count_fn`` (see
+    ``diagnostics.order_statistics``) replace the two HIP calls (tests of this logic); without ``linpred_fn`` a CPU tensor
+    raises HipLibraryError. Not with an active process group."""
+    import math
+
+    from . import _abi
+
+    members, held, firsts, per, n_draws = _predict_plan(x, target, chains_per_group)
+    probs = [float(p) for p in (probs.tolist() if hasattr(probs, "tolist") else probs)]
+    if not probs or any(not (0.0 <= p <= 1.0) for p in probs):
+        raise ValueError("probs must be a non-empty sequence of numbers in [0, 1] (got %r)" % (probs,))
+    table, n_new = _predicted(target, members, X_new)
+    G, Q, S = len(members), len(probs), per * n_draws
+    chains = per * G
+    # the interpolation of diagnostics.quantiles: h = p (S - 1), lo = floor(h), v[lo] + (v[min(lo + 1, S - 1)] - v[lo]) (h - lo)
+    h = [p * (S - 1) for p in probs]
+    lo = [int(math.floor(v)) for v in h]
+    hi = [min(k + 1, S - 1) for k in lo]
+    ranks = [0, S - 1] + lo + hi
+    # scratch: an observation block of eta, and one group's select counts of it (256 buckets x 64 columns x 8 bytes a rank)
+    unit = chains * n_draws * 64 * 8
+    count_unit = 256 * 64 * 8 * min(len(set(ranks)), _abi.SELECT_MAX_RANKS)
+    nob = (n_new + 63) // 64
+    step = min(int(scratch_bytes) // (unit + count_unit), nob)
+    if step < 1:
+        raise ValueError("scratch_bytes=%d is below one block of 64 observations of the linear predictor, %d chains x %d draws "
+                         "x 64 x 8 = %d bytes, plus %d bytes of the select's counts of it" % (int(scratch_bytes), chains, n_draws,
+                                                                                              unit, count_unit))
+    if linpred_fn is None:
+        for b in held:
+            diagnostics._device_block(b)     # HipLibraryError for a CPU tensor: there is no host implementation
+    dev = held[0].device
+    frac = torch.tensor([a - b for a, b in zip(h, lo)], dtype=torch.float64, device=dev).reshape(Q, 1)
+    liks = [m.likelihood for m in members]
+    cache = True if X_new is None else {}   # where the table of parameter rows lives on the devices
+    moments, eta_q, mu_q = [], [], []
+    for ob0 in range(0, nob, step):
+        ob1 = min(ob0 + step, nob)
+        W = 64 * (ob1 - ob0)
+        etas, tot = [], torch.zeros((G, len(MOMENT_PLANES), W), dtype=torch.float64, device=dev)
+        parts = []
+        for b, f in zip(held, firsts):   # one kernel per device, all enqueued before the first result is moved
+            eta, st = _linpred_block(b, target, table, cache, f, per, ob0, ob1, linpred_fn)
+            etas.append(eta)
+            parts.append((f // per, st))
+        for off, st in parts:
+            st = st.to(dev)
+            tot[off:off + st.shape[0]] = merge_moments(tot[off:off + st.shape[0]], st)
+        os_ = diagnostics.order_statistics(etas if len(etas) > 1 else etas[0], ranks, chains_per_group=per,
+                                           scratch_bytes=int(scratch_bytes) - (ob1 - ob0) * unit, count_fn=count_fn)
+        del etas, eta
+        vmin, vmax = os_[:, 0], os_[:, 1]
+        vlo, vhi = os_[:, 2:2 + Q], os_[:, 2 + Q:]
+        bad = (torch.isnan(vmin) | torch.isnan(vmax)).unsqueeze(1)      # a NaN draw: every quantile NaN, as numpy's are
+        nan = torch.full((G, Q, W), float("nan"), dtype=torch.float64, device=dev)
+        eta_q.append(torch.where(bad, nan, vlo + (vhi - vlo) * frac))
+        mlo = torch.stack([_inverse_link(liks[g], vlo[g]) for g in range(G)])
+        mhi = torch.stack([_inverse_link(liks[g], vhi[g]) for g in range(G)])
+        mu_q.append(torch.where(bad, nan, mlo + (mhi - mlo) * frac))
+        moments.append(tot)
+    tot = torch.cat(moments, dim=-1)[..., :n_new]
+    n = tot[:, 0]
+    eta_mean, mu_mean = tot[:, 1], tot[:, 3]
+    eta_var, mu_var = tot[:, 2] / (n - 1.0), tot[:, 4] / (n - 1.0)
+    sig2 = torch.tensor([float(m.sigma) ** 2 for m in members], dtype=torch.float64, device=dev).reshape(G, 1)
+    is_b = torch.tensor([k == "bernoulli" for k in liks], device=dev).reshape(G, 1)
+    is_p = torch.tensor([k == "poisson" for k in liks], device=dev).reshape(G, 1)
+    y_mean = torch.where(is_b | is_p, mu_mean, eta_mean)
+    y_var = torch.where(is_b, mu_mean * (1.0 - mu_mean), torch.where(is_p, mu_mean + mu_var, sig2 + eta_var))
+    return dict(eta_mean=eta_mean, eta_sd=torch.sqrt(eta_var), mu_mean=mu_mean, mu_sd=torch.sqrt(mu_var),
+                eta_quantiles=torch.cat(eta_q, dim=-1)[..., :n_new], mu_quantiles=torch.cat(mu_q, dim=-1)[..., :n_new],
+                y_mean=y_mean, y_var=y_var, n=S, probs=probs)

@@ -242,6 +242,14 @@ class GLM(DeviceTarget):
 
         return predictive.loo(x, self, **kw)
 
+    def predict(self, x, X_new=None, **kw):
+        """``predictive.predict(x, self, X_new, ...)``: posterior predictions at the points ``X_new[N_new, d]`` (default: the
+        training design) from the draws ``x`` in HBM (leading axis 1) -- mean and sd of the linear predictor and of the mean
+        response, their exact credible bands, and the mean and variance of a new response."""
+        from . import predictive
+
+        return predictive.predict(x, self, X_new, **kw)
+
     def __repr__(self):
         return "GLM(%s, N=%d, d=%d)" % (self.likelihood, self.n_obs, self.d)
 
@@ -754,6 +762,14 @@ class Batched(DeviceTarget):
         from . import predictive
 
         return predictive.loo(x, self, **kw)
+
+    def predict(self, x, X_new=None, **kw):
+        """``predictive.predict(x, self, X_new, ...)`` per posterior (GLM members): predictions at ``X_new``, a list of G arrays
+        ``[N_new, d]`` with one common N_new (default: each member's training design) -- ``eta_mean[G, N_new]``,
+        ``mu_quantiles[G, Q, N_new]``, ``y_mean``, ``y_var``, ... of all groups from the draws in HBM."""
+        from . import predictive
+
+        return predictive.predict(x, self, X_new, **kw)
 
     def __repr__(self):
         return "Batched(%d x %s, d=%d)" % (self.groups, type(self.members[0]).__name__, self.d)
