@@ -19,11 +19,13 @@
 // (lmc_target_param_row), and the statistics are wanted per group. The block index is (group, chain block, slab); a block
 // loops over ITS group's chains inside the trace block, and the reduction adds a group's chain blocks. The ~4096
 // wavefronts of a launch are shared by the groups, so many small groups get one block each and the partial buffer stays
-// at the size of the result. The ungrouped call is the one-group call of the same code.
+// at the size of the result. The ungrouped call is the one-group call of the same code. The entry point's checks of the trace
+// view and of the grouping are trace_span (lmc_trace_pass.hpp), shared by every pass over the trace.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/lmc_hip.h"
+#include "lmc_trace_pass.hpp"
 
 namespace lmc {
 
@@ -140,14 +142,10 @@ extern "C" int lmc_diag_chain_stats_grouped(const double* x, int64_t chains, int
                                             void* stream) {
     using namespace lmc;
     const int64_t lim = int64_t(1) << 31;
-    if (!x || !out || chains < 1 || dim < 1 || n < 2 || t0 < 0 || t0 + n > draws_stride || lag0 < 0) return LMC_ERR_INVALID;
-    if (first_chain < 0 || chains_per_group < 1 || chains >= lim || first_chain >= lim || first_chain + chains >= lim)
+    TraceSpan span;
+    if (!out || n < 2 || lag0 < 0 || trace_span(x, chains, draws_stride, dim, t0, n, first_chain, chains_per_group, &span) != LMC_OK)
         return LMC_ERR_INVALID;
-    const int64_t per = chains_per_group < lim ? chains_per_group : lim - 1;   // (no job chain has an index >= 2^31: the same groups)
-    int64_t g0 = 0, g1 = 0;                             // the groups of the block's first and last chain
-    if (lmc_target_param_row(0, first_chain, per, &g0) != LMC_OK || lmc_target_param_row(chains - 1, first_chain, per, &g1) != LMC_OK)
-        return LMC_ERR_INVALID;
-    const int64_t groups = g1 - g0 + 1;
+    const int64_t per = span.per, g0 = span.g0, groups = span.groups;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int nslab = (dim + 63) / 64;
     long long cbl = (4096 / nslab) / groups;            // ~16 wavefronts per CU, each looping over chains: shared by the groups

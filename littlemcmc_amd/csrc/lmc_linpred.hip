@@ -18,12 +18,15 @@
 // no scratch, no atomics. Per (draw, observation) the kernel moves 8 bytes out (the eta store) and d / 8 L2-resident loads of
 // X in (one per coefficient and kPredT draws); the trace row comes through the scalar unit, once per wave and tile.
 // At d = 32 the store is the floor: the kernel is a write stream of chains x draws x W doubles.
+// The entry point's checks of the trace view, the grouping and the GLM table are trace_span, glm_span and glm_check_headers
+// (lmc_trace_pass.hpp), shared by every pass over the trace.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/lmc_hip.h"
 #include "lmc_predict_tile.hpp"
 #include "lmc_targets.hpp"
+#include "lmc_trace_pass.hpp"
 
 namespace lmc {
 
@@ -160,19 +163,12 @@ extern "C" int lmc_glm_linpred(const double* x, int64_t chains, int64_t draws_st
                                int64_t ob0, int64_t ob1, double* eta, double* stats, void* stream) {
     using namespace lmc;
     const int64_t lim = int64_t(1) << 31;
-    if (!x || !rows || (!eta && !stats) || chains < 1 || dim < 1 || n < 1 || t0 < 0 || t0 + n > draws_stride) return LMC_ERR_INVALID;
-    if (first_chain < 0 || chains_per_group < 1 || chains >= lim || first_chain >= lim || first_chain + chains >= lim)
+    TraceSpan span;
+    GlmSpan glm;
+    if ((!eta && !stats) || trace_span(x, chains, draws_stride, dim, t0, n, first_chain, chains_per_group, &span) != LMC_OK ||
+        glm_span(rows, row_len, n_rows, dim, span, ob0, ob1, &glm) != LMC_OK)
         return LMC_ERR_INVALID;
-    if (dim > LMC_GLM_MAX_DIM || n_rows < 1) return LMC_ERR_INVALID;
-    const int64_t npad = glm_npad_of_row(row_len, dim);
-    if (npad < 64) return LMC_ERR_INVALID;
-    if (ob0 < 0 || ob1 <= ob0 || ob1 > npad / 64) return LMC_ERR_INVALID;
-    const int64_t per = chains_per_group < lim ? chains_per_group : lim - 1;
-    int64_t g0 = 0, g1 = 0;
-    if (lmc_target_param_row(0, first_chain, per, &g0) != LMC_OK || lmc_target_param_row(chains - 1, first_chain, per, &g1) != LMC_OK)
-        return LMC_ERR_INVALID;
-    if (g1 >= n_rows) return LMC_ERR_INVALID;
-    const int64_t groups = g1 - g0 + 1;
+    const int64_t per = span.per, g0 = span.g0, groups = span.groups, npad = glm.npad;
     const int64_t nobr = ob1 - ob0, W = nobr * 64;
     // eta[chains][n][W] of 2^40 elements or more is refused: chains < 2^31 and W < 2^29, so chains * W cannot overflow, and
     // the kernels index with 64 bits throughout (the launch limits below are the tighter ones)
@@ -183,7 +179,7 @@ extern "C" int lmc_glm_linpred(const double* x, int64_t chains, int64_t draws_st
     if (blocks >= lim || (total + 255) / 256 >= lim) return LMC_ERR_INVALID;
     hipStream_t s = static_cast<hipStream_t>(stream);
     // the headers of the touched rows: one strided copy, the call's only host look, before anything is launched
-    const int hdr_rc = glm_check_headers(rows, row_len, g0, groups, npad, dim, s);
+    const int hdr_rc = glm_check_headers(rows, row_len, span, npad, dim, s);
     if (hdr_rc != LMC_OK) return hdr_rc;
     double* partial = nullptr;
     if (stats) {

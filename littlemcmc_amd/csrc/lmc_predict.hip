@@ -24,14 +24,15 @@
 // Non-finite l (include/lmc_hip.h says the same): a draw with l = -inf (an overflowing poisson exp(eta)) contributes
 // exp(l - m) := 0 whatever m is, so m and S are those of the other draws and m + log S stays finite (all draws -inf:
 // m = -inf, S = 0); mean and M2 are then non-finite (-inf or NaN) and sum mu = +inf. A NaN l makes planes 1..5 NaN.
+// The entry point's checks of the trace view, the grouping and the GLM table are trace_span, glm_span and glm_check_headers
+// (lmc_trace_pass.hpp), shared by every pass over the trace.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-
-#include <vector>
 
 #include "../../include/lmc_hip.h"
 #include "lmc_predict_tile.hpp"
 #include "lmc_targets.hpp"
+#include "lmc_trace_pass.hpp"
 
 namespace lmc {
 
@@ -166,19 +167,12 @@ extern "C" int lmc_glm_pointwise(const double* x, int64_t chains, int64_t draws_
                                  int64_t chains_per_group, double* out, void* stream) {
     using namespace lmc;
     const int64_t lim = int64_t(1) << 31;
-    if (!x || !out || !rows || chains < 1 || dim < 1 || n < 1 || t0 < 0 || t0 + n > draws_stride) return LMC_ERR_INVALID;
-    if (first_chain < 0 || chains_per_group < 1 || chains >= lim || first_chain >= lim || first_chain + chains >= lim)
+    TraceSpan span;
+    GlmSpan glm;   // every block of 64 observations: [0, nob)
+    if (!out || trace_span(x, chains, draws_stride, dim, t0, n, first_chain, chains_per_group, &span) != LMC_OK ||
+        glm_span(rows, row_len, n_rows, dim, span, 0, glm_npad_of_row(row_len, dim) / 64, &glm) != LMC_OK)
         return LMC_ERR_INVALID;
-    if (dim > LMC_GLM_MAX_DIM || n_rows < 1) return LMC_ERR_INVALID;
-    const int64_t npad = glm_npad_of_row(row_len, dim);
-    if (npad < 64) return LMC_ERR_INVALID;
-    const int64_t per = chains_per_group < lim ? chains_per_group : lim - 1;
-    int64_t g0 = 0, g1 = 0;
-    if (lmc_target_param_row(0, first_chain, per, &g0) != LMC_OK || lmc_target_param_row(chains - 1, first_chain, per, &g1) != LMC_OK)
-        return LMC_ERR_INVALID;
-    if (g1 >= n_rows) return LMC_ERR_INVALID;
-    const int64_t groups = g1 - g0 + 1;
-    const int64_t nob = npad / 64;
+    const int64_t per = span.per, g0 = span.g0, groups = span.groups, npad = glm.npad, nob = glm.nob;
     long long cbl = (4096 / nob) / groups;   // one launch-wide budget of wavefronts, shared by the groups
     if (cbl > per) cbl = per;
     if (cbl > chains) cbl = chains;
@@ -189,7 +183,7 @@ extern "C" int lmc_glm_pointwise(const double* x, int64_t chains, int64_t draws_
     if (blocks >= lim || (total + 255) / 256 >= lim) return LMC_ERR_INVALID;
     hipStream_t s = static_cast<hipStream_t>(stream);
     // the headers of the touched rows: one strided copy, the call's only host look, before anything is launched
-    const int hdr_rc = glm_check_headers(rows, row_len, g0, groups, npad, dim, s);
+    const int hdr_rc = glm_check_headers(rows, row_len, span, npad, dim, s);
     if (hdr_rc != LMC_OK) return hdr_rc;
     double* partial = nullptr;
     const size_t bytes = static_cast<size_t>(blocks) * kPredPlanes * 64 * sizeof(double);

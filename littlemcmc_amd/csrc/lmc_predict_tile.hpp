@@ -8,11 +8,10 @@
 // address (the scalar unit, one load for 64 lanes) and NEVER beyond its d coefficients -- the trace is [.., d], the next
 // doubles are the next draw -- and every loaded X element feeds kPredT FMAs, eta[i] = fma(Xt[e][n], q_i[e], eta[i]) with e
 // ascending: the functor's eta (lmc_targets.hpp: GLMTarget), bit for bit. Then the link, the functor's expressions.
+// Device code only: the entry points' host-side checks of a GLM table are in lmc_trace_pass.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-
-#include <vector>
 
 #include "../../include/lmc_hip.h"
 #include "lmc_targets.hpp"
@@ -100,41 +99,6 @@ __device__ __forceinline__ void glm_link_tile(const double* qt, int k, int dim, 
     double eta[kPredT];
     glm_eta_tile(qt, k, dim, xt, col0, row_bytes, eta);
     glm_link_of_eta(lik, yn, isig2, eta, l, mu);
-}
-
-// npad of a GLM row of row_len doubles at dimension dim, or 0 if no N gives that length (pure arithmetic)
-inline int64_t glm_npad_of_row(int64_t row_len, int32_t dim) {
-    int64_t ns = 1;
-    while (ns * 64 < dim) ns *= 2;
-    const int64_t per_obs = 1 + (dim + 7) / 8 * 8 + 64 * ns;
-    if (row_len <= LMC_GLM_HEADER || row_len >= LMC_GLM_MAX_ROW || (row_len - LMC_GLM_HEADER) % per_obs != 0) return 0;
-    const int64_t npad = (row_len - LMC_GLM_HEADER) / per_obs;
-    return (npad % 64 == 0) ? npad : 0;
-}
-
-// The headers of the rows [g0, g0 + groups) of a DEVICE table: one strided copy on s, the entry points' only host look,
-// before anything is launched. LMC_ERR_INVALID for a header that disagrees with dim or row_len (npad) or carries an
-// unknown likelihood code.
-inline int glm_check_headers(const double* rows, int64_t row_len, int64_t g0, int64_t groups, int64_t npad, int32_t dim,
-                             hipStream_t s) {
-    std::vector<double> hdr(static_cast<size_t>(groups) * LMC_GLM_HEADER);
-    if (hipMemcpy2DAsync(hdr.data(), LMC_GLM_HEADER * sizeof(double), rows + g0 * row_len, static_cast<size_t>(row_len) * sizeof(double),
-                         LMC_GLM_HEADER * sizeof(double), static_cast<size_t>(groups), hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess) {
-        (void)hipGetLastError();
-        return LMC_ERR_HIP;
-    }
-    int64_t ns = 1;
-    while (ns * 64 < dim) ns *= 2;
-    for (int64_t i = 0; i < groups; ++i) {
-        const double* h = hdr.data() + i * LMC_GLM_HEADER;
-        const bool lik_ok = h[0] == LMC_GLM_BERNOULLI || h[0] == LMC_GLM_POISSON || h[0] == LMC_GLM_GAUSSIAN;
-        const bool n_ok = h[1] >= 1.0 && h[1] <= static_cast<double>(npad) && h[1] > static_cast<double>(npad - 64);
-        if (!lik_ok || !n_ok || h[2] != static_cast<double>(npad) || h[5] != static_cast<double>(dim) ||
-            h[6] != static_cast<double>(64 * ns))
-            return LMC_ERR_INVALID;
-    }
-    return LMC_OK;
 }
 
 }  // namespace lmc

@@ -20,12 +20,15 @@
 // Every floating-point sum is taken in a fixed order -- a thread's elements ascending, the wavefront by a xor butterfly, the
 // wavefronts ascending -- so two calls on the same data give the same bits. LDS: the tail (32 KiB), the histogram (2 KiB),
 // the fit's partial sums and candidates (5 KiB) and a few scalars, 40 KiB in all.
+// lmc_glm_pointwise_loglik's checks of the trace view, the grouping and the GLM table are trace_span, glm_span and
+// glm_check_headers (lmc_trace_pass.hpp), shared by every pass over the trace; lmc_psis_rows is no such pass.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/lmc_hip.h"
 #include "lmc_predict_tile.hpp"
 #include "lmc_targets.hpp"
+#include "lmc_trace_pass.hpp"
 
 namespace lmc {
 
@@ -298,23 +301,18 @@ extern "C" int lmc_glm_pointwise_loglik(const double* x, int64_t chains, int64_t
                                         int64_t chains_per_group, int64_t ob0, int64_t ob1, double* out, void* stream) {
     using namespace lmc;
     const int64_t lim = int64_t(1) << 31;
-    if (!x || !out || !rows || chains < 1 || dim < 1 || n < 1 || t0 < 0 || t0 + n > draws_stride) return LMC_ERR_INVALID;
-    if (first_chain < 0 || chains_per_group < 1 || chains >= lim || first_chain >= lim || first_chain + chains >= lim)
-        return LMC_ERR_INVALID;
-    if (dim > LMC_GLM_MAX_DIM || n_rows < 1) return LMC_ERR_INVALID;
-    if (first_chain % chains_per_group != 0 || chains % chains_per_group != 0) return LMC_ERR_INVALID;   // whole groups
-    const int64_t npad = glm_npad_of_row(row_len, dim);
-    if (npad < 64) return LMC_ERR_INVALID;
-    const int64_t nob = npad / 64;
-    if (ob0 < 0 || ob1 <= ob0 || ob1 > nob) return LMC_ERR_INVALID;
-    const int64_t per = chains_per_group;
-    const int64_t g0 = first_chain / per, groups = chains / per;
-    if (g0 + groups > n_rows) return LMC_ERR_INVALID;
+    TraceSpan span;
+    GlmSpan glm;
+    if (!out || trace_span(x, chains, draws_stride, dim, t0, n, first_chain, chains_per_group, &span) != LMC_OK) return LMC_ERR_INVALID;
+    // whole groups: then chains_per_group <= chains < 2^31 (span.per is it), g0 = first_chain / per and groups = chains / per
+    if (first_chain % chains_per_group != 0 || chains % chains_per_group != 0) return LMC_ERR_INVALID;
+    if (glm_span(rows, row_len, n_rows, dim, span, ob0, ob1, &glm) != LMC_OK) return LMC_ERR_INVALID;
+    const int64_t per = span.per, g0 = span.g0, npad = glm.npad;
     const int64_t nobr = ob1 - ob0;
     const int64_t blocks = chains * nobr;
     if (blocks >= lim) return LMC_ERR_INVALID;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int hdr_rc = glm_check_headers(rows, row_len, g0, groups, npad, dim, s);
+    const int hdr_rc = glm_check_headers(rows, row_len, span, npad, dim, s);
     if (hdr_rc != LMC_OK) return hdr_rc;
     (void)hipGetLastError();
     hipLaunchKernelGGL(pointwise_loglik_kernel, dim3(static_cast<unsigned>(blocks)), dim3(64), 0, s, x,

@@ -20,10 +20,12 @@
 // of a pass run together): once at shift 56, and e.g. twice at W = 32 with 8 ranks -- three probabilities' lo / hi ranks,
 // the minimum and the maximum. Algorithmic bytes of a pass: 8 x chains x n x dim x that factor.
 // A 32-bit counter cannot wrap: the host gives a block at most (2^32 - 1) / n chains, so no block counts 2^32 draws.
+// The entry point's checks of the trace view and of the grouping are trace_span (lmc_trace_pass.hpp).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/lmc_hip.h"
+#include "lmc_trace_pass.hpp"
 
 namespace lmc {
 
@@ -114,16 +116,12 @@ extern "C" int lmc_select_digit_counts(const double* x, int64_t chains, int64_t 
                                        const uint64_t* prefix, int64_t* counts, void* stream) {
     using namespace lmc;
     const int64_t lim = int64_t(1) << 31;
-    if (!x || !counts || chains < 1 || dim < 1 || n < 1 || n >= lim || t0 < 0 || t0 + n > draws_stride) return LMC_ERR_INVALID;
-    if (first_chain < 0 || chains_per_group < 1 || chains >= lim || first_chain >= lim || first_chain + chains >= lim)
+    TraceSpan span;
+    if (!counts || n >= lim || trace_span(x, chains, draws_stride, dim, t0, n, first_chain, chains_per_group, &span) != LMC_OK)
         return LMC_ERR_INVALID;
     if (shift < 0 || shift > 56 || shift % 8 != 0 || n_ranks < 1 || n_ranks > LMC_SELECT_MAX_RANKS) return LMC_ERR_INVALID;
     if (shift == 56 ? n_ranks != 1 : !prefix) return LMC_ERR_INVALID;
-    const int64_t per = chains_per_group < lim ? chains_per_group : lim - 1;   // (no job chain has an index >= 2^31: the same groups)
-    int64_t g0 = 0, g1 = 0;                             // the groups of the block's first and last chain
-    if (lmc_target_param_row(0, first_chain, per, &g0) != LMC_OK || lmc_target_param_row(chains - 1, first_chain, per, &g1) != LMC_OK)
-        return LMC_ERR_INVALID;
-    const int64_t groups = g1 - g0 + 1;
+    const int64_t per = span.per, g0 = span.g0, groups = span.groups;
     const int w = dim <= 16 ? 16 : (dim <= 32 ? 32 : 64);
     const int slots = kSelTable / (256 * w);
     const int nslab = (dim + w - 1) / w, ntile = (n_ranks + slots - 1) / slots;

@@ -24,6 +24,7 @@ the test oracle's restatement of the kernel's block (oracle/diagnostics_oracle.p
 Posterior quantiles, equal-tailed credible intervals and tail-ESS (``order_statistics``, ``quantiles``, ``intervals``,
 ``tail_ess``, at the end of this module) follow the same rule with an integer statistic: a radix select whose passes are
 histograms of key digits from ``lmc_select_digit_counts`` (csrc/lmc_select.hip), exact and additive over chains and GPUs."""
+import collections
 import ctypes
 import math
 
@@ -43,22 +44,32 @@ def _hip_chain_stats(x, t0, n, lag0, first_chain=None, per=None):
     """One pass of lmc_diag_chain_stats over x[chains, draws, d] (float64, contiguous, on a ROCm device):
     -> [3 + 16, d] float64 tensor on the same device. With ``per`` chains per group, x's chain 0 being chain ``first_chain`` of
     the job, one pass of lmc_diag_chain_stats_grouped: -> [groups touched, 3 + 16, d]."""
-    from . import _abi
-
-    lib = _abi.load()
-    c, _n, d = x.shape
-    stride = x.stride(0) // d if c > 1 else _n     # rows of a chain lie d apart; chains `stride` rows apart (_row_major)
     name, grouping, lead = "lmc_diag_chain_stats", (), ()
     if per is not None:
-        name, grouping, lead = "lmc_diag_chain_stats_grouped", (int(first_chain), int(per)), (_touched(first_chain, c, per)[1],)
-    out = torch.empty(lead + (3 + LAGS_PER_PASS, d), dtype=torch.float64, device=x.device)
+        name, grouping = "lmc_diag_chain_stats_grouped", (int(first_chain), int(per))
+        lead = (_touched(first_chain, int(x.shape[0]), per)[1],)
+    out = torch.empty(lead + (3 + LAGS_PER_PASS, int(x.shape[2])), dtype=torch.float64, device=x.device)
+    _call_trace_kernel(name, x, int(lag0), *grouping, out, t0=t0, n=n)
+    return out
+
+
+def _call_trace_kernel(name, x, *args, t0=0, n=None):
+    """The one call of an entry point that makes a pass over the trace (include/lmc_hip.h): ``name(x, chains, draws_stride, d,
+    t0, n, *args, stream)`` on x's device and current stream, over the sub-series [t0, t0 + n) of every chain (default: all
+    draws). x[chains, draws, d] goes as the kernel reads it (_device_block: HipLibraryError for a CPU tensor); a tensor among
+    ``args`` goes as its device pointer, None as NULL. RuntimeError unless the call returns LMC_OK."""
+    from . import _abi
+
+    x = _device_block(x)
+    c, rows, d = x.shape
+    stride = x.stride(0) // d if c > 1 else rows     # rows of a chain lie d apart; chains `stride` rows apart (_row_major)
     with torch.cuda.device(x.device):
         stream = torch.cuda.current_stream(x.device).cuda_stream
-        rc = getattr(lib, name)(ctypes.c_void_p(x.data_ptr()), c, stride, d, int(t0), int(n), int(lag0), *grouping,
-                                ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(stream))
+        rc = getattr(_abi.load(), name)(ctypes.c_void_p(x.data_ptr()), c, stride, d, int(t0), int(rows if n is None else n),
+                                        *[ctypes.c_void_p(a.data_ptr()) if torch.is_tensor(a) else a for a in args],
+                                        ctypes.c_void_p(stream))
     if rc != 0:
         raise RuntimeError("%s failed (status %d)" % (name, rc))
-    return out
 
 
 def _row_major(x):
@@ -68,16 +79,94 @@ def _row_major(x):
     return x.stride(2) == 1 and x.stride(1) == d and (c <= 1 or (x.stride(0) % d == 0 and x.stride(0) >= n * d))
 
 
-def _blocks(x):
-    """x is one tensor [chains, draws, d], or a list of them: the chain blocks of ONE job that this process holds on
-    several GPUs (sample(..., devices=[...]) -> trace_tensor(group)). Reductions land on the first block's device."""
-    return list(x) if isinstance(x, (list, tuple)) else [x]
-
-
 def _touched(first_chain, chains, per):
     """(g0, number of groups) that the job's chains [first_chain, first_chain + chains) touch, ``per`` chains a group."""
     g0 = first_chain // per
     return g0, (first_chain + chains - 1) // per - g0 + 1
+
+
+# ---- a pass over the trace: the job (what is x?) and the fan-out (one kernel per device, the parts combined) --------------
+# held: the blocks that hold chains, in job order; firsts: the job chain of each one's chain 0; chains: their total; per:
+# chains per group; the chains touch the groups [g0, g0 + groups); n_draws, d: of every block; device: of the first block.
+TraceJob = collections.namedtuple("TraceJob", "held firsts chains per g0 groups n_draws d device")
+
+
+def _trace_job(x, chains_per_group=None, first_chain=0, target=None, whole_job=False, whole_groups=False,
+               allow_first_chain=False):
+    """The TraceJob of x: one tensor [chains, draws, d], or the list of the chain blocks of ONE job that this process holds on
+    several GPUs (sample(..., devices=[...]) -> trace_tensor(group)), in job order -- and every refusal of such an x. Blocks
+    without chains are dropped first; the others agree in draws and in d (``target.d``, with a target). ``chains_per_group``
+    defaults to ``target.group_size(chains)`` (a ``targets.Batched``) or to one group of all chains. The rules a pass chooses:
+    ``allow_first_chain``: x's first chain may be chain ``first_chain`` > 0 of the job (without: x is the whole job);
+    ``whole_job``: the chains are all the chains of every posterior -- ``per`` times the target's groups, a multiple of ``per``
+    without a target; ``whole_groups``: no group straddles two blocks. Not with an active process group."""
+    blocks, first_chain = list(x) if isinstance(x, (list, tuple)) else [x], int(first_chain)
+    if not blocks or any(b.dim() != 3 for b in blocks):
+        raise ValueError("x must be [chains, draws, d] or a non-empty list of such blocks")
+    if _group_active():
+        raise ValueError("a pass over the trace with an active process group (sample_distributed) is not supported: it is "
+                         "taken within one process (pass the list of its per-GPU blocks), not reduced across ranks")
+    if first_chain != 0 and not allow_first_chain:
+        raise ValueError("first_chain=%d: this x is the whole job (for this pass a list of blocks is), its first block starts at "
+                         "chain 0" % first_chain)
+    held = [b for b in blocks if b.shape[0] > 0]
+    firsts = [first_chain + sum(int(a.shape[0]) for a in held[:i]) for i in range(len(held))]
+    if not held:
+        raise ValueError("x holds no chain")
+    if len({int(b.shape[2]) for b in held}) > 1:
+        raise ValueError("the chain blocks differ in d: %s" % [int(b.shape[2]) for b in held])
+    if len({int(b.shape[1]) for b in held}) > 1:
+        raise ValueError("the chain blocks hold different numbers of draws per chain: %s" % [int(b.shape[1]) for b in held])
+    chains, n_draws, d = firsts[-1] + int(held[-1].shape[0]) - first_chain, int(held[0].shape[1]), int(held[0].shape[2])
+    if n_draws < 1 or d < 1:
+        raise ValueError("x holds no draw")
+    if target is not None and d != target.d:
+        raise ValueError("x has d = %d, the target d = %d" % (d, target.d))
+    if chains_per_group is not None:
+        per = int(chains_per_group)
+    elif hasattr(target, "group_size"):
+        if first_chain != 0:
+            raise ValueError("a block of a Batched job that starts at first_chain=%d needs chains_per_group" % first_chain)
+        per = target.group_size(chains)
+    else:
+        per = first_chain + chains
+    if per < 1 or first_chain < 0:
+        raise ValueError("chains_per_group must be >= 1 and first_chain >= 0 (got %d, %d)" % (per, first_chain))
+    g0, groups = _touched(first_chain, chains, per)
+    if target is not None:
+        rows = getattr(target, "groups", 1)
+        if whole_job and per * rows != chains:
+            raise ValueError("%d chains at %d chains per group are not the %d posteriors of the target" % (chains, per, rows))
+        if g0 + groups > rows:
+            raise ValueError("chains %d .. %d at %d chains per group reach group %d; the target has %d"
+                             % (first_chain, first_chain + chains - 1, per, g0 + groups - 1, rows))
+    elif whole_job and chains % per != 0:
+        raise ValueError("chains_per_group=%d needs a multiple of %d chains (got chains=%d)" % (per, per, chains))
+    if whole_groups and any(f % per != 0 for f in firsts):
+        raise ValueError("at %d chains per group a group straddles two chain blocks (blocks of %s chains); the draws of one "
+                         "posterior form one row and need to lie on one device" % (per, [int(b.shape[0]) for b in held]))
+    return TraceJob(held, firsts, chains, per, g0, groups, n_draws, d, held[0].device)
+
+
+def _fan_out(job, ga, gb, call, combine):
+    """One pass over the groups [ga, gb) of a job -> [gb - ga, ...] on ``job.device``. ``call(block, first_chain)`` runs the
+    kernel on the part of those groups' chains that a block holds, on the block's own device, and returns [groups the part
+    touches, ...]; every block's call is enqueued before the first result moves. The parts are then folded, in job order,
+    into a block of zeros at their group offsets: ``combine(so far, part)`` is ``torch.add`` for sums and counts, or a merge
+    that skips a side of count 0 by its count (predictive.merge, merge_moments) -- so zeros are the identity of each, and a
+    group that straddles two blocks is the combination of its parts."""
+    parts = []
+    for b, f in zip(job.held, job.firsts):
+        lo, hi = max(ga * job.per, f), min(gb * job.per, f + int(b.shape[0]))
+        if lo < hi:
+            parts.append((lo // job.per - ga, call(b[lo - f:hi - f], lo)))
+    tot = None
+    for off, part in parts:
+        part = part.to(job.device)
+        if tot is None:
+            tot = torch.zeros((gb - ga,) + tuple(part.shape[1:]), dtype=part.dtype, device=job.device)
+        tot[off:off + part.shape[0]] = combine(tot[off:off + part.shape[0]], part)
+    return tot
 
 
 def chain_stats_pass(x, ranges, lag0, stats_fn=None, chains_per_group=None, first_chain=0):
@@ -86,16 +175,9 @@ def chain_stats_pass(x, ranges, lag0, stats_fn=None, chains_per_group=None, firs
     that are present. A list of blocks (in job order) is added up: a group that straddles two blocks is the sum of its parts."""
     if isinstance(x, (list, tuple)):   # one kernel per device, all enqueued before the first result is moved
         if chains_per_group is not None:
-            per, firsts = int(chains_per_group), [int(first_chain)]
-            for b in x:
-                firsts.append(firsts[-1] + int(b.shape[0]))
-            parts = [(f, chain_stats_pass(b, ranges, lag0, stats_fn, per, f)) for f, b in zip(firsts, x) if b.shape[0] > 0]
-            g0, touched = _touched(firsts[0], max(firsts[-1] - firsts[0], 1), per)
-            tot = torch.zeros((touched, 3 + LAGS_PER_PASS, int(x[0].shape[2])), dtype=torch.float64, device=x[0].device)
-            for f, p_ in parts:
-                off = f // per - g0
-                tot[off:off + p_.shape[0]] += p_.to(tot.device)
-            return tot
+            job = _trace_job(x, chains_per_group, first_chain, allow_first_chain=True)
+            return _fan_out(job, job.g0, job.g0 + job.groups,
+                            lambda b, f: _chain_stats_pass_grouped(b, ranges, lag0, stats_fn, job.per, f), torch.add)
         parts = [chain_stats_pass(b, ranges, lag0, stats_fn) for b in x]
         tot = parts[0]
         for p_ in parts[1:]:
@@ -210,7 +292,7 @@ def sufficient_stats(x, split=True, max_lag=None, group=None, reduce_device=None
     ``chains_per_group=per``: the job's chains (the blocks, in job order) are G = chains / per posteriors of ``per``
     consecutive chains; every statistic gets a leading [G] axis, ``n_chains`` is the chains (times halves) of ONE group, and
     the passes continue until Geyer's sequence has ended in every dimension of every group -- still one host look per pass."""
-    blocks = _blocks(x)
+    blocks = list(x) if isinstance(x, (list, tuple)) else [x]   # (no TraceJob: a rank of a process group may hold no chain)
     held = [b for b in blocks if b.shape[0] > 0]
     if len({int(b.shape[1]) for b in held}) > 1:
         raise ValueError("the chain blocks hold different numbers of draws per chain: %s" % [int(b.shape[1]) for b in held])
@@ -511,12 +593,7 @@ _INT64_MIN = -(1 << 63)
 def _hip_select_counts(x, first_chain, per, shift, prefix):
     """One call of lmc_select_digit_counts over x[chains, draws, d] (a ROCm tensor): -> [groups touched, n_ranks, 256, d] int64
     on x's device. ``prefix`` is [groups touched, n_ranks, d] int64 on that device (None at shift 56: one rank slot)."""
-    from . import _abi
-
-    lib = _abi.load()
-    x = _device_block(x)
-    c, n, d = x.shape
-    stride = x.stride(0) // d if c > 1 else n
+    c, _n, d = x.shape
     touched = _touched(first_chain, c, per)[1]
     n_ranks = 1 if prefix is None else int(prefix.shape[1])
     if prefix is not None:
@@ -524,64 +601,28 @@ def _hip_select_counts(x, first_chain, per, shift, prefix):
         if tuple(prefix.shape) != (touched, n_ranks, d) or prefix.dtype != torch.int64 or prefix.device != x.device:
             raise ValueError("prefix must be int64 [%d, n_ranks, %d] on %s" % (touched, d, x.device))
     out = torch.empty((touched, n_ranks, 256, d), dtype=torch.int64, device=x.device)
-    with torch.cuda.device(x.device):
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        rc = lib.lmc_select_digit_counts(ctypes.c_void_p(x.data_ptr()), c, stride, d, 0, n, int(first_chain), int(per), int(shift),
-                                         n_ranks, ctypes.c_void_p(prefix.data_ptr()) if prefix is not None else None,
-                                         ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(stream))
-    if rc != 0:
-        raise RuntimeError("lmc_select_digit_counts failed (status %d)" % rc)
+    _call_trace_kernel("lmc_select_digit_counts", x, int(first_chain), int(per), int(shift), n_ranks, prefix, out)
     return out
 
 
 def _select_job(x, chains_per_group):
-    """(blocks that hold chains, their first job chains, per, G, n, d) of an order-statistics job; refusals."""
-    blocks = _blocks(x)
-    if not blocks:
-        raise ValueError("no chain block")
-    if _group_active():
-        raise ValueError("quantiles with an active process group: order statistics are taken within one process (pass the "
-                         "list of its per-GPU blocks), not reduced across ranks")
-    if any(b.dim() != 3 for b in blocks):
-        raise ValueError("draws must be [chains, draws, d]")
-    if len({int(b.shape[2]) for b in blocks}) > 1:
-        raise ValueError("the chain blocks differ in d: %s" % [int(b.shape[2]) for b in blocks])
-    firsts, held = [], []
-    c = 0
-    for b in blocks:
-        if b.shape[0] > 0:
-            firsts.append(c)
-            held.append(b)
-        c += int(b.shape[0])
-    if len({int(b.shape[1]) for b in held}) > 1:
-        raise ValueError("the chain blocks hold different numbers of draws per chain: %s" % [int(b.shape[1]) for b in held])
-    if not held or held[0].shape[1] < 1 or held[0].shape[2] < 1:
-        raise ValueError("no draws: x is empty")
-    per = c if chains_per_group is None else _chains_per_group(c, chains_per_group)
-    return held, firsts, per, c // per, int(held[0].shape[1]), int(held[0].shape[2])
+    """The TraceJob of an order-statistics job: the whole job, all chains of every group; a group may straddle blocks."""
+    return _trace_job(x, chains_per_group, whole_job=True)
 
 
-def _select_counts(held, firsts, per, ga, gb, shift, prefix, count_fn, dev):
-    """Digit counts [gb - ga, n_ranks, 256, d] of the groups [ga, gb) of the job, on ``dev``: every block counts the part of
-    those groups' chains it holds, on its own device (all enqueued before the first result moves), and the parts are added."""
+def _select_counts(job, ga, gb, shift, prefix, count_fn):
+    """Digit counts [gb - ga, n_ranks, 256, d] of the groups [ga, gb) of the job, on ``job.device``: every block counts the
+    part of those groups' chains it holds, on its own device, and the parts are added (_fan_out)."""
     fn = _hip_select_counts if count_fn is None else count_fn
-    parts = []
-    for b, f in zip(held, firsts):
-        lo, hi = max(ga * per, f), min(gb * per, f + int(b.shape[0]))
-        if lo >= hi:
-            continue
-        off, touched = _touched(lo, hi - lo, per)
-        pf = None if prefix is None else prefix[off - ga:off - ga + touched].to(b.device)
-        parts.append((off - ga, fn(b[lo - f:hi - f], lo, per, shift, pf)))
-    tot = None
-    for off, p_ in parts:
-        if tot is None and off == 0 and p_.shape[0] == gb - ga:
-            tot = p_.to(dev)
-            continue
-        if tot is None:
-            tot = torch.zeros((gb - ga,) + tuple(p_.shape[1:]), dtype=torch.int64, device=dev)
-        tot[off:off + p_.shape[0]] += p_.to(dev)
-    return tot
+
+    def call(b, first):
+        off, touched = _touched(first, int(b.shape[0]), job.per)
+        return fn(b, first, job.per, shift, None if prefix is None else prefix[off - ga:off - ga + touched].to(b.device))
+
+    for b, f in zip(job.held, job.firsts):   # one block holds all these chains: its counts are the sum -- moved, not added to
+        if f <= ga * job.per and gb * job.per <= f + int(b.shape[0]):   # zeros (exact for integers, and half the memory)
+            return call(b[ga * job.per - f:gb * job.per - f], ga * job.per).to(job.device)
+    return _fan_out(job, ga, gb, call, torch.add)
 
 
 def order_statistics(x, ranks, chains_per_group=None, scratch_bytes=1 << 30, count_fn=None):
@@ -602,8 +643,8 @@ def order_statistics(x, ranks, chains_per_group=None, scratch_bytes=1 << 30, cou
     active process group."""
     from . import _abi
 
-    held, firsts, per, G, n, d = _select_job(x, chains_per_group)
-    S = per * n
+    job = _select_job(x, chains_per_group)
+    G, d, dev, S = job.groups, job.d, job.device, job.per * job.n_draws
     want = [int(r) for r in ranks]
     if not want:
         raise ValueError("no ranks")
@@ -616,15 +657,11 @@ def order_statistics(x, ranks, chains_per_group=None, scratch_bytes=1 << 30, cou
     if chunk < 1:
         raise ValueError("scratch_bytes=%d is below the %d bytes of one group's counts (%d ranks x 256 x %d dimensions x 8)"
                          % (scratch_bytes, unit, max(len(r) for r in rounds), d))
-    dev = held[0].device
-    if count_fn is None:
-        for b in held:
-            _device_block(b)     # HipLibraryError for a CPU tensor: there is no host implementation
     out = torch.empty((G, len(uniq), d), dtype=torch.float64, device=dev)
     for ga in range(0, G, chunk):
         gb = min(ga + chunk, G)
         # the shift-56 pass is shared by the rounds; the cumulative counts overwrite the counts (no second table)
-        first = _select_counts(held, firsts, per, ga, gb, SELECT_SHIFTS[0], None, count_fn, dev).cumsum_(2)
+        first = _select_counts(job, ga, gb, SELECT_SHIFTS[0], None, count_fn).cumsum_(2)
         q0 = 0
         for rks in rounds:
             rem = torch.tensor(rks, dtype=torch.int64, device=dev).reshape(1, -1, 1).expand(gb - ga, len(rks), d).contiguous()
@@ -633,7 +670,7 @@ def order_statistics(x, ranks, chains_per_group=None, scratch_bytes=1 << 30, cou
                 if shift == SELECT_SHIFTS[0]:
                     cum = first.expand(-1, len(rks), -1, -1)                      # [g, ranks, 256, d]
                 else:
-                    cum = _select_counts(held, firsts, per, ga, gb, shift, prefix, count_fn, dev).cumsum_(2)
+                    cum = _select_counts(job, ga, gb, shift, prefix, count_fn).cumsum_(2)
                 bucket = (cum <= rem.unsqueeze(2)).sum(dim=2).clamp_(max=255)     # the first bucket whose cumulative count passes
                 below = torch.gather(cum, 2, (bucket - 1).clamp_(min=0).unsqueeze(2)).squeeze(2)
                 rem = rem - torch.where(bucket > 0, below, torch.zeros_like(below))
@@ -659,8 +696,8 @@ def quantiles(x, probs, chains_per_group=None, **kw):
     probs = [float(p) for p in (probs.tolist() if hasattr(probs, "tolist") else probs)]
     if not probs or any(not (0.0 <= p <= 1.0) for p in probs):
         raise ValueError("probs must be a non-empty sequence of numbers in [0, 1] (got %r)" % (probs,))
-    held, _firsts, per, _G, n, _d = _select_job(x, chains_per_group)
-    S = per * n
+    job = _select_job(x, chains_per_group)
+    S = job.per * job.n_draws
     h = [p * (S - 1) for p in probs]
     lo = [int(math.floor(v)) for v in h]
     hi = [min(k + 1, S - 1) for k in lo]
@@ -694,7 +731,8 @@ def tail_ess(x, probs=(0.05, 0.95), split=True, chains_per_group=None, chunk_dim
     chunk_dims doubles, the bound rank_normalize keeps -- and goes through ``sufficient_stats`` / ``finalize`` like any draws.
     ``**kw`` goes to ``order_statistics``; ``stats_fn`` to ``sufficient_stats``."""
     q = quantiles(x, probs, chains_per_group=chains_per_group, **kw)["quantiles"]
-    held, firsts, per, G, n, d = _select_job(x, chains_per_group)
+    job = _select_job(x, chains_per_group)
+    held, firsts, per, G, d = job.held, job.firsts, job.per, job.groups, job.d
     best = None
     for k in range(q.shape[-2]):
         parts = []

@@ -12,7 +12,13 @@ one backend, the HIP kernel; the merge / finalise logic above it is plain tensor
 restatement of the kernel's block through ``stats_fn`` (as ``diagnostics.summarize`` does).
 
 Further down: PSIS-LOO (``psis``, ``loo``; csrc/lmc_psis.hip) and posterior predictions at new X (``linear_predictor``,
-``predict``; csrc/lmc_linpred.hip), each with its own kernel and its own injected model in the CPU tests."""
+``predict``; csrc/lmc_linpred.hip), each with its own kernel and its own injected model in the CPU tests.
+
+What the passes over the trace share is stated once, in ``diagnostics``: ``_trace_job`` answers "what is x?" (one tensor or
+the per-GPU blocks of a job, chains per group, the groups touched) with every refusal, each pass naming the rule it wants in
+one line; ``_fan_out`` runs a kernel on every block's device and folds the parts with :func:`merge` / :func:`merge_moments`;
+``_call_trace_kernel`` is the ctypes call. Here remain the kernels' outputs, the parameter table on the devices
+(:func:`_table_on`) and the statistics."""
 import ctypes
 import weakref
 
@@ -35,17 +41,20 @@ def merge(a, b):
     A side of count 0 is skipped BY ITS COUNT: the other side comes through bit for bit, whatever the empty side holds."""
     na, ma, Sa, mea, M2a, mua = a.unbind(-2)
     nb, mb, Sb, meb, M2b, mub = b.unbind(-2)
-    n = na + nb
     hi, lo = torch.maximum(ma, mb), torch.minimum(ma, mb)
     e = torch.where(torch.isneginf(lo), torch.zeros_like(lo), torch.exp(lo - hi))   # (-inf) - (-inf) is never used
     S = torch.where(ma >= mb, Sa + Sb * e, Sa * e + Sb)
-    safe = torch.where(n > 0, n, torch.ones_like(n))
-    delta = meb - mea
-    mean = mea + delta * (nb / safe)
-    M2 = (M2a + M2b) + (delta * delta) * (na * nb / safe)
-    both = torch.stack([n, hi, S, mean, M2, mua + mub], dim=-2)
+    both = torch.stack([na + nb, hi, S, *_chan(na, mea, M2a, nb, meb, M2b), mua + mub], dim=-2)
     only_a, only_b = (nb == 0).unsqueeze(-2), (na == 0).unsqueeze(-2)
     return torch.where(only_a, a, torch.where(only_b, b, both))
+
+
+def _chan(na, mean_a, M2_a, nb, mean_b, M2_b):
+    """Chan's update of a (mean, M2) pair over disjoint sets of na and nb draws (na + nb = 0: finite junk, never selected)."""
+    n = na + nb
+    safe = torch.where(n > 0, n, torch.ones_like(n))
+    delta = mean_b - mean_a
+    return mean_a + delta * (nb / safe), (M2_a + M2_b) + (delta * delta) * (na * nb / safe)
 
 
 def _members(target):
@@ -88,26 +97,18 @@ def _hip_pointwise(x, table, first_chain, per):
     from . import _abi
     from .targets import glm_row_layout
 
-    lib = _abi.load()
-    c, n, d = x.shape
-    stride = x.stride(0) // d if c > 1 else n
+    c, _n, d = x.shape
     n_rows, row_len = table.shape
     npad = (row_len - _abi.GLM_HEADER) // (glm_row_layout(1, d)["size"] - _abi.GLM_HEADER) * 64
     out = torch.empty((diagnostics._touched(first_chain, c, per)[1], len(PLANES), npad), dtype=torch.float64, device=x.device)
-    with torch.cuda.device(x.device):
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        rc = lib.lmc_glm_pointwise(ctypes.c_void_p(x.data_ptr()), c, stride, d, 0, n, ctypes.c_void_p(table.data_ptr()),
-                                   row_len, n_rows, int(first_chain), int(per), ctypes.c_void_p(out.data_ptr()),
-                                   ctypes.c_void_p(stream))
-    if rc != 0:
-        raise RuntimeError("lmc_glm_pointwise failed (status %d)" % rc)
+    diagnostics._call_trace_kernel("lmc_glm_pointwise", x, table, row_len, n_rows, int(first_chain), int(per), out)
     return out
 
 
-def _table_on(target, table, device, cache):
-    if not cache:
-        return torch.as_tensor(table).to(device)
-    held = _device_rows.setdefault(target, {})
+def _table_on(target, table, device, cache=None):
+    """The host table of parameter rows on ``device``, copied there once per ``cache``: a dict device -> table of this call, or
+    (None: the table is the target's own) the dict that lives and dies with the target."""
+    held = _device_rows.setdefault(target, {}) if cache is None else cache
     key = str(device)
     if key not in held:
         held[key] = torch.as_tensor(table).to(device)
@@ -127,65 +128,25 @@ def pointwise_stats(x, target, data=None, chains_per_group=None, first_chain=0, 
     list of G such pairs with one common N -- scores held-out data under the posterior draws: the same ``d``, ``y`` validated
     as ``GLM`` validates it, any N. ``stats_fn(x, table, first_chain, per) -> [groups touched, 6, >= N]`` replaces the HIP
     call (tests of the merge and finalise logic only; ``table`` is then the host table of parameter rows)."""
-    from .targets import Batched
-
     members = _members(target)
-    if group is not None or diagnostics._group_active(group):
+    if group is not None:
         raise ValueError("pointwise predictive statistics are a one-process matter: group= / an active process group "
                          "(sample_distributed) is not supported")
-    is_list = isinstance(x, (list, tuple))
-    blocks = list(x) if is_list else [x]
-    first_chain = int(first_chain)
-    if is_list and first_chain != 0:
-        raise ValueError("first_chain=%d with a list of blocks: the list is the whole job, its first block starts at chain 0"
-                         % first_chain)
-    if not blocks or any(b.dim() != 3 for b in blocks):
-        raise ValueError("x must be [chains, draws, d] or a list of such blocks")
-    held = [b for b in blocks if b.shape[0] > 0]
-    if not held:
-        raise ValueError("x holds no chain")
-    if len({(int(b.shape[1]), int(b.shape[2])) for b in held}) > 1:
-        raise ValueError("the chain blocks differ in draws per chain or in d: %s" % [tuple(b.shape[1:]) for b in held])
-    n_draws, d = int(held[0].shape[1]), int(held[0].shape[2])
-    if d != members[0].d:
-        raise ValueError("x has d = %d, the target d = %d" % (d, members[0].d))
-    if n_draws < 1:
-        raise ValueError("x holds no draw")
-    chains = sum(int(b.shape[0]) for b in blocks)
-    if chains_per_group is None:
-        per = target.group_size(chains) if isinstance(target, Batched) and first_chain == 0 else None
-        if per is None:
-            if isinstance(target, Batched):
-                raise ValueError("a block of a Batched job that starts at first_chain=%d needs chains_per_group" % first_chain)
-            per = first_chain + chains
-    else:
-        per = int(chains_per_group)
-    if per < 1 or first_chain < 0:
-        raise ValueError("chains_per_group must be >= 1 and first_chain >= 0 (got %d, %d)" % (per, first_chain))
-    g0, touched = diagnostics._touched(first_chain, chains, per)
-    if g0 + touched > len(members):
-        raise ValueError("chains %d .. %d at %d chains per group reach group %d; the target has %d"
-                         % (first_chain, first_chain + chains - 1, per, g0 + touched - 1, len(members)))
+    # one tensor may start inside the job, a list is the whole job; a group may straddle blocks
+    job = diagnostics._trace_job(x, chains_per_group, first_chain, target, allow_first_chain=not isinstance(x, (list, tuple)))
     table, scored = _scored(target, members, data)
     n_obs = scored[0].n_obs
-    dev = blocks[0].device
-    parts, f = [], first_chain
-    for b in blocks:   # one kernel per device, all enqueued before the first result is moved
-        c = int(b.shape[0])
-        if c > 0:
-            if stats_fn is not None:
-                blk = stats_fn(b, table, f, per)
-            else:
-                b = diagnostics._device_block(b)
-                blk = _hip_pointwise(b, _table_on(target, table, b.device, data is None), f, per)
-            parts.append((f // per - g0, blk[..., :n_obs]))
-        f += c
-    tot = torch.zeros((touched, len(PLANES), n_obs), dtype=torch.float64, device=dev)
-    for off, blk in parts:
-        blk = blk.to(dev)
-        tot[off:off + blk.shape[0]] = merge(tot[off:off + blk.shape[0]], blk)
+    cache = None if data is None else {}   # where the table of parameter rows lives on the devices
+
+    def call(b, first):
+        if stats_fn is not None:
+            return stats_fn(b, table, first, job.per)[..., :n_obs]
+        b = diagnostics._device_block(b)
+        return _hip_pointwise(b, _table_on(target, table, b.device, cache), first, job.per)[..., :n_obs]
+
+    tot = diagnostics._fan_out(job, job.g0, job.g0 + job.groups, call, merge)
     out = {name: tot[:, i] for i, name in enumerate(PLANES)}
-    out["first_group"] = g0
+    out["first_group"] = job.g0
     return out
 
 
@@ -320,62 +281,19 @@ def psis(loglik, reff=1.0, psis_fn=None):
 
 def _hip_loglik(x, table, first_chain, per, ob0, ob1):
     """One call of lmc_glm_pointwise_loglik: x[chains, draws, d] holding whole groups -> [groups, 64 (ob1 - ob0), per * draws]."""
-    from . import _abi
-
-    lib = _abi.load()
-    c, n, d = x.shape
-    stride = x.stride(0) // d if c > 1 else n
+    c, n, _d = x.shape
     n_rows, row_len = table.shape
     out = torch.empty((c // per, 64 * (ob1 - ob0), per * n), dtype=torch.float64, device=x.device)
-    with torch.cuda.device(x.device):
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        rc = lib.lmc_glm_pointwise_loglik(ctypes.c_void_p(x.data_ptr()), c, stride, d, 0, n, ctypes.c_void_p(table.data_ptr()),
-                                          row_len, n_rows, int(first_chain), int(per), int(ob0), int(ob1),
-                                          ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(stream))
-    if rc != 0:
-        raise RuntimeError("lmc_glm_pointwise_loglik failed (status %d)" % rc)
+    diagnostics._call_trace_kernel("lmc_glm_pointwise_loglik", x, table, row_len, n_rows, int(first_chain), int(per), int(ob0),
+                                   int(ob1), out)
     return out
-
-
-def _loo_plan(x, target):
-    """The blocks of a LOO / pointwise_loglik job: (members, blocks, firsts, per, n_draws, table)."""
-    from .targets import Batched
-
-    members = _members(target)
-    if diagnostics._group_active(None):
-        raise ValueError("PSIS-LOO is a one-process matter: an active process group (sample_distributed) is not supported")
-    blocks = list(x) if isinstance(x, (list, tuple)) else [x]
-    if not blocks or any(b.dim() != 3 for b in blocks):
-        raise ValueError("x must be [chains, draws, d] or a list of such blocks")
-    held = [b for b in blocks if b.shape[0] > 0]
-    if not held:
-        raise ValueError("x holds no chain")
-    if len({(int(b.shape[1]), int(b.shape[2])) for b in held}) > 1:
-        raise ValueError("the chain blocks differ in draws per chain or in d: %s" % [tuple(b.shape[1:]) for b in held])
-    n_draws, d = int(held[0].shape[1]), int(held[0].shape[2])
-    if d != members[0].d:
-        raise ValueError("x has d = %d, the target d = %d" % (d, members[0].d))
-    if n_draws < 1:
-        raise ValueError("x holds no draw")
-    chains = sum(int(b.shape[0]) for b in blocks)
-    per = target.group_size(chains) if isinstance(target, Batched) else chains
-    firsts, f = [], 0
-    for b in blocks:
-        firsts.append(f)
-        f += int(b.shape[0])
-    if any(f % per != 0 for f in firsts):
-        raise ValueError("PSIS-LOO at %d chains per group: a group straddles two chain blocks (blocks of %s chains); the "
-                         "draws of one posterior form one row and need to lie on one device"
-                         % (per, [int(b.shape[0]) for b in blocks]))
-    table = np.ascontiguousarray(target.params, dtype=np.float64).reshape(len(members), -1)
-    return members, blocks, firsts, per, n_draws, table
 
 
 def _loglik_block(b, target, table, first, per, ob0, ob1, loglik_fn):
     if loglik_fn is not None:
         return loglik_fn(b, table, first, per, ob0, ob1)
     b = diagnostics._device_block(b)
-    return _hip_loglik(b, _table_on(target, table, b.device, True), first, per, ob0, ob1)
+    return _hip_loglik(b, _table_on(target, table, b.device), first, per, ob0, ob1)
 
 
 def pointwise_loglik(x, target, groups=None, obs_blocks=None, loglik_fn=None):
@@ -385,19 +303,19 @@ def pointwise_loglik(x, target, groups=None, obs_blocks=None, loglik_fn=None):
     trace: meant for tests and small jobs, :func:`loo` walks it in chunks. ``groups=(g0, g1)`` and ``obs_blocks=(ob0, ob1)``
     select half-open ranges of groups and of blocks of 64 observations (default: all). ``x`` as for :func:`waic`; with a
     list of per-GPU blocks every group must lie in one block, and the result is gathered on the first block's device."""
-    members, blocks, firsts, per, n_draws, table = _loo_plan(x, target)
+    members = _members(target)
+    job = diagnostics._trace_job(x, None, 0, target, whole_job=True, whole_groups=True)   # a posterior's draws form one row
+    table, per = np.ascontiguousarray(target.params, dtype=np.float64).reshape(len(members), -1), job.per
     nob = (members[0].n_obs + 63) // 64
     g_lo, g_hi = (0, len(members)) if groups is None else (int(groups[0]), int(groups[1]))
     ob0, ob1 = (0, nob) if obs_blocks is None else (int(obs_blocks[0]), int(obs_blocks[1]))
     if not (0 <= g_lo < g_hi <= len(members)) or not (0 <= ob0 < ob1 <= nob):
         raise ValueError("groups=%r of %d, obs_blocks=%r of %d: half-open, non-empty ranges" % (groups, len(members), obs_blocks, nob))
     parts = []
-    for b, f in zip(blocks, firsts):
+    for b, f in zip(job.held, job.firsts):   # (a gather of whole groups, not a fan-out: nothing is combined)
         lo, hi = max(g_lo, f // per), min(g_hi, (f + int(b.shape[0])) // per)
         if lo < hi:
             parts.append(_loglik_block(b[lo * per - f:hi * per - f], target, table, lo * per, per, ob0, ob1, loglik_fn))
-    if not parts:
-        raise ValueError("groups=%r lie in no block of x" % (groups,))
     return parts[0] if len(parts) == 1 else torch.cat([p.to(parts[0].device) for p in parts], dim=0)
 
 
@@ -419,8 +337,10 @@ def loo(x, target, reff=1.0, scratch_bytes=1 << 30, psis_fn=None, loglik_fn=None
     if data is not None:
         raise ValueError("loo() is in-sample: leave-one-out of the training data has no data= (waic(x, data=...) scores "
                          "held-out points)")
-    members, blocks, firsts, per, n_draws, table = _loo_plan(x, target)
-    S = per * n_draws
+    members = _members(target)
+    job = diagnostics._trace_job(x, None, 0, target, whole_job=True, whole_groups=True)   # a posterior's draws form one row
+    table, per = np.ascontiguousarray(target.params, dtype=np.float64).reshape(len(members), -1), job.per
+    S = per * job.n_draws
     M = _checked_tail_len(S, reff)
     n_obs = members[0].n_obs
     nob = (n_obs + 63) // 64
@@ -432,7 +352,7 @@ def loo(x, target, reff=1.0, scratch_bytes=1 << 30, psis_fn=None, loglik_fn=None
     out = waic(x, target, **kw)
     dev = out["lppd"].device
     rows = torch.empty((len(members), nob * 64, len(PSIS_COLUMNS)), dtype=torch.float64, device=dev)
-    for b, f in zip(blocks, firsts):   # each block on its own device; the small results move to the first one
+    for b, f in zip(job.held, job.firsts):   # each block on its own device; the small results move to the first one
         g_b, n_g = f // per, int(b.shape[0]) // per
         if cap >= nob:
             chunks = [(g, min(g + cap // nob, n_g), 0, nob) for g in range(0, n_g, cap // nob)]
@@ -465,11 +385,7 @@ def merge_moments(a, b):
     BY ITS COUNT: the other side comes through bit for bit, whatever the empty side holds."""
     na, mea, M2a, mma, N2a = a.unbind(-2)
     nb, meb, M2b, mmb, N2b = b.unbind(-2)
-    n = na + nb
-    safe = torch.where(n > 0, n, torch.ones_like(n))
-    w, cross = nb / safe, na * nb / safe
-    de, dm = meb - mea, mmb - mma
-    both = torch.stack([n, mea + de * w, (M2a + M2b) + (de * de) * cross, mma + dm * w, (N2a + N2b) + (dm * dm) * cross], dim=-2)
+    both = torch.stack([na + nb, *_chan(na, mea, M2a, nb, meb, M2b), *_chan(na, mma, N2a, nb, mmb, N2b)], dim=-2)
     only_a, only_b = (nb == 0).unsqueeze(-2), (na == 0).unsqueeze(-2)
     return torch.where(only_a, a, torch.where(only_b, b, both))
 
@@ -505,75 +421,23 @@ def _predicted(target, members, X_new):
 def _hip_linpred(x, table, first_chain, per, ob0, ob1, want_eta=True, want_stats=True):
     """One call of lmc_glm_linpred: x[chains, draws, d] (float64, _row_major, on a ROCm device), table[n_rows, row_len] on the
     same device -> (eta[chains, draws, W] or None, stats[groups touched, 5, W] or None), W = 64 (ob1 - ob0)."""
-    from . import _abi
-
-    lib = _abi.load()
-    c, n, d = x.shape
-    stride = x.stride(0) // d if c > 1 else n
+    c, n, _d = x.shape
     n_rows, row_len = table.shape
     W = 64 * (int(ob1) - int(ob0))
     eta = torch.empty((c, n, W), dtype=torch.float64, device=x.device) if want_eta else None
     stats = (torch.empty((diagnostics._touched(first_chain, c, per)[1], len(MOMENT_PLANES), W), dtype=torch.float64, device=x.device)
              if want_stats else None)
-    with torch.cuda.device(x.device):
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        rc = lib.lmc_glm_linpred(ctypes.c_void_p(x.data_ptr()), c, stride, d, 0, n, ctypes.c_void_p(table.data_ptr()), row_len,
-                                 n_rows, int(first_chain), int(per), int(ob0), int(ob1),
-                                 ctypes.c_void_p(eta.data_ptr()) if want_eta else None,
-                                 ctypes.c_void_p(stats.data_ptr()) if want_stats else None, ctypes.c_void_p(stream))
-    if rc != 0:
-        raise RuntimeError("lmc_glm_linpred failed (status %d)" % rc)
+    diagnostics._call_trace_kernel("lmc_glm_linpred", x, table, row_len, n_rows, int(first_chain), int(per), int(ob0), int(ob1),
+                                   eta, stats)
     return eta, stats
 
 
 def _linpred_block(b, target, table, cache, first, per, ob0, ob1, linpred_fn, want_eta=True, want_stats=True):
-    """``cache``: the table is the target's own (kept on the device with the target) or a dict device -> table of this call."""
+    """``cache``: as for :func:`_table_on` -- None where the table is the target's own, a dict of this call for ``X_new``."""
     if linpred_fn is not None:
         return linpred_fn(b, table, first, per, ob0, ob1, want_eta, want_stats)
     b = diagnostics._device_block(b)
-    if cache is True:
-        tab = _table_on(target, table, b.device, True)
-    else:
-        key = str(b.device)
-        if key not in cache:
-            cache[key] = torch.as_tensor(table).to(b.device)
-        tab = cache[key]
-    return _hip_linpred(b, tab, first, per, ob0, ob1, want_eta, want_stats)
-
-
-def _predict_plan(x, target, chains_per_group):
-    """The blocks of a prediction job: (members, blocks that hold chains, their first job chains, per, n_draws)."""
-    from .targets import Batched
-
-    members = _members(target)
-    if diagnostics._group_active(None):
-        raise ValueError("posterior predictions are a one-process matter: an active process group (sample_distributed) is not "
-                         "supported")
-    blocks = list(x) if isinstance(x, (list, tuple)) else [x]
-    if not blocks or any(b.dim() != 3 for b in blocks):
-        raise ValueError("x must be [chains, draws, d] or a list of such blocks")
-    held, firsts, f = [], [], 0
-    for b in blocks:
-        if b.shape[0] > 0:
-            held.append(b)
-            firsts.append(f)
-        f += int(b.shape[0])
-    if not held:
-        raise ValueError("x holds no chain")
-    if len({(int(b.shape[1]), int(b.shape[2])) for b in held}) > 1:
-        raise ValueError("the chain blocks differ in draws per chain or in d: %s" % [tuple(b.shape[1:]) for b in held])
-    n_draws, d = int(held[0].shape[1]), int(held[0].shape[2])
-    if d != members[0].d:
-        raise ValueError("x has d = %d, the target d = %d" % (d, members[0].d))
-    if n_draws < 1:
-        raise ValueError("x holds no draw")
-    if chains_per_group is None:
-        per = target.group_size(f) if isinstance(target, Batched) else f
-    else:
-        per = int(chains_per_group)
-    if per < 1 or per * len(members) != f:
-        raise ValueError("%d chains at %d chains per group are not the %d posteriors of the target" % (f, per, len(members)))
-    return members, held, firsts, per, n_draws
+    return _hip_linpred(b, _table_on(target, table, b.device, cache), first, per, ob0, ob1, want_eta, want_stats)
 
 
 def linear_predictor(x, target, X_new=None, obs_blocks=None, linpred_fn=None):
@@ -586,13 +450,14 @@ def linear_predictor(x, target, X_new=None, obs_blocks=None, linpred_fn=None):
     first_chain, per, ob0, ob1, want_eta, want_stats) -> (eta, stats[groups touched, 5, W])`` replaces the HIP call."""
     if isinstance(x, (list, tuple)):
         raise ValueError("linear_predictor takes one tensor; predict() takes the list of per-GPU blocks of a job")
-    members, held, firsts, per, _n = _predict_plan(x, target, None)
+    members = _members(target)
+    job = diagnostics._trace_job(x, None, 0, target, whole_job=True)
     table, n_new = _predicted(target, members, X_new)
     nob = (n_new + 63) // 64
     ob0, ob1 = (0, nob) if obs_blocks is None else (int(obs_blocks[0]), int(obs_blocks[1]))
     if not (0 <= ob0 < ob1 <= nob):
         raise ValueError("obs_blocks=%r of %d: a half-open, non-empty range" % (obs_blocks, nob))
-    eta, st = _linpred_block(held[0], target, table, True if X_new is None else {}, 0, per, ob0, ob1, linpred_fn)
+    eta, st = _linpred_block(job.held[0], target, table, None if X_new is None else {}, 0, job.per, ob0, ob1, linpred_fn)
     return eta, {name: st[:, i] for i, name in enumerate(MOMENT_PLANES)}
 
 
@@ -633,8 +498,10 @@ def predict(x, target, X_new=None, probs=(0.05, 0.5, 0.95), chains_per_group=Non
 
     from . import _abi
 
-    members, held, firsts, per, n_draws = _predict_plan(x, target, chains_per_group)
-    probs = [float(p) for p in (probs.tolist() if hasattr(probs, "tolist") else probs)]
+    members = _members(target)
+    job = diagnostics._trace_job(x, chains_per_group, 0, target, whole_job=True)   # a group may straddle blocks
+    per, n_draws, dev = job.per, job.n_draws, job.device
+    probs =[float(p) for p in (probs.tolist() if hasattr(probs, "tolist") else probs)]
     if not probs or any(not (0.0 <= p <= 1.0) for p in probs):
         raise ValueError("probs must be a non-empty sequence of numbers in [0, 1] (got %r)" % (probs,))
     table, n_new = _predicted(target, members, X_new)
@@ -654,29 +521,23 @@ def predict(x, target, X_new=None, probs=(0.05, 0.5, 0.95), chains_per_group=Non
         raise ValueError("scratch_bytes=%d is below one block of 64 observations of the linear predictor, %d chains x %d draws "
                          "x 64 x 8 = %d bytes, plus %d bytes of the select's counts of it" % (int(scratch_bytes), chains, n_draws,
                                                                                               unit, count_unit))
-    if linpred_fn is None:
-        for b in held:
-            diagnostics._device_block(b)     # HipLibraryError for a CPU tensor: there is no host implementation
-    dev = held[0].device
-    frac = torch.tensor([a - b for a, b in zip(h, lo)], dtype=torch.float64, device=dev).reshape(Q, 1)
+    frac =torch.tensor([a - b for a, b in zip(h, lo)], dtype=torch.float64, device=dev).reshape(Q, 1)
     liks = [m.likelihood for m in members]
-    cache = True if X_new is None else {}   # where the table of parameter rows lives on the devices
-    moments, eta_q, mu_q = [], [], []
+    cache = None if X_new is None else {}   # where the table of parameter rows lives on the devices
+    moments, eta_q, mu_q, etas = [], [], [], []
+
+    def call(b, first):   # the eta of the block stays on its device for the select; its moments are the part to merge
+        eta, st = _linpred_block(b, target, table, cache, first, per, ob0, ob1, linpred_fn)
+        etas.append(eta)
+        return st
+
     for ob0 in range(0, nob, step):
         ob1 = min(ob0 + step, nob)
         W = 64 * (ob1 - ob0)
-        etas, tot = [], torch.zeros((G, len(MOMENT_PLANES), W), dtype=torch.float64, device=dev)
-        parts = []
-        for b, f in zip(held, firsts):   # one kernel per device, all enqueued before the first result is moved
-            eta, st = _linpred_block(b, target, table, cache, f, per, ob0, ob1, linpred_fn)
-            etas.append(eta)
-            parts.append((f // per, st))
-        for off, st in parts:
-            st = st.to(dev)
-            tot[off:off + st.shape[0]] = merge_moments(tot[off:off + st.shape[0]], st)
+        tot = diagnostics._fan_out(job, 0, G, call, merge_moments)
         os_ = diagnostics.order_statistics(etas if len(etas) > 1 else etas[0], ranks, chains_per_group=per,
                                            scratch_bytes=int(scratch_bytes) - (ob1 - ob0) * unit, count_fn=count_fn)
-        del etas, eta
+        del etas[:]
         vmin, vmax = os_[:, 0], os_[:, 1]
         vlo, vhi = os_[:, 2:2 + Q], os_[:, 2 + Q:]
         bad = (torch.isnan(vmin) | torch.isnan(vmax)).unsqueeze(1)      # a NaN draw: every quantile NaN, as numpy's are
