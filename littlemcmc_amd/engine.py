@@ -249,6 +249,74 @@ def _target_grouping(target, chains, first_chain, chains_per_group):
     return first_chain, chains_per_group
 
 
+def engine_config(lib, target, chains, kind="nuts", potential="diag_adapt", device=0,
+                  target_accept=0.8, Emax=1000.0, adapt_step_size=True, step_scale=0.25, gamma=0.05, k=0.75,
+                  t0=10, path_length=2.0, max_treedepth=10, early_max_treedepth=8, max_steps=1024,
+                  adaptation_window=101, adaptation_window_multiplier=1.0, lds_levels=0, sdot=None, rng="numpy",
+                  mass_dtype="float32", lds_plan="auto", tuning=None):
+    """The lmc_config an Engine with these arguments hands to lmc_engine_create, and whether its mass matrix is float64:
+    (cfg, mass_f64). Pure: ``lib`` is asked for the defaults only (lmc_config_defaults: no device, no HIP call)."""
+    chains, dim = int(chains), int(target.d)
+    cfg = _abi.Config()
+    lib.lmc_config_defaults(C.byref(cfg), chains, dim)
+    cfg.device = int(device)
+    cfg.kind = {"nuts": _abi.KIND_NUTS, "hmc": _abi.KIND_HMC}[kind]
+    cfg.target_family = int(target.family)
+    cfg.potential = {"diag_adapt": _abi.POT_DIAG_ADAPT, "diag": _abi.POT_DIAG, "full": _abi.POT_FULL,
+                     "full_inv": _abi.POT_FULL_INV, "full_adapt": _abi.POT_FULL_ADAPT, "full_f64": _abi.POT_FULL_F64}[potential]
+    cfg.adapt_step_size = int(bool(adapt_step_size))
+    cfg.target_accept = float(target_accept)
+    cfg.emax = float(Emax)
+    cfg.step_scale = float(step_scale)
+    cfg.gamma = float(gamma)
+    cfg.k = float(k)
+    cfg.t0 = float(t0)
+    cfg.max_treedepth = int(max_treedepth)
+    cfg.early_max_treedepth = int(early_max_treedepth)
+    cfg.path_length = float(path_length)
+    cfg.max_steps = int(max_steps)
+    cfg.adaptation_window = int(adaptation_window)
+    cfg.adaptation_window_multiplier = float(adaptation_window_multiplier)
+    cfg.lds_levels = int(lds_levels)
+    # include/lmc_hip.h: LMC_LDS_PLAN_* (results do not depend on it; pinned values are for A/B runs and parity tests). Like
+    # the lmc_tuning knobs, the variable the LIBRARY used to read (LMC_LDS_PLAN=0 / 1) is still honoured -- by the host, and
+    # only when the caller left the choice open (tools/ab_lds_plan.sh, tools/sample_path_rate.py)
+    if lds_plan in ("auto", None):
+        import os
+
+        lds_plan = {"0": 0, "1": 1}.get(os.environ.get("LMC_LDS_PLAN", ""), "auto")
+    cfg.lds_plan = {"auto": _abi.LDS_PLAN_AUTO, None: _abi.LDS_PLAN_AUTO, 0: _abi.LDS_PLAN_SHALLOW, "shallow": _abi.LDS_PLAN_SHALLOW,
+                    1: _abi.LDS_PLAN_DEEP, "deep": _abi.LDS_PLAN_DEEP}[lds_plan]
+    for field, value in (tuning_from_env() if tuning is None else dict(tuning)).items():   # struct lmc_tuning: test / A-B knobs
+        setattr(cfg.tuning, field, int(value))
+    if cfg.tuning.sub_blocks == 0 and hw_queue_cap() is not None:   # left open: at most one sub-block per hardware queue
+        cfg.tuning.sub_blocks = -hw_queue_cap()
+    cfg.rng_mode = {"numpy": _abi.RNG_NUMPY, "philox": _abi.RNG_PHILOX, "counter": _abi.RNG_COUNTER}[rng]   # include/lmc_hip.h: LMC_RNG_*
+    # QuadPotentialDiagAdapt(dtype=...) (quadpotential.py:159,175-184); float64 runs in the general kernels
+    # QuadPotentialFullAdapt(dtype=...) (quadpotential.py:484,497-509) likewise: float64 covariance, factor and momentum
+    mass_f64 = np.dtype(mass_dtype) == np.float64 and potential in ("diag_adapt", "diag", "full_adapt")
+    cfg.mass_f64 = int(mass_f64)
+    if cfg.target_family == _abi.TARGET_EXTERNAL:
+        # a density evaluated by the caller (a torch / Python callable) is driven by the tick kernels, which exist for the
+        # fused shapes and for float32 diagonals beyond them (include/lmc_hip.h: "Which kernels an engine runs")
+        if potential not in ("diag_adapt", "diag") and dim > 256:
+            raise NotImplementedError("a density given as a torch / Python callable runs with dense mass matrices up to "
+                                      "model_ndim = 256 (got %d); give it as a device functor (targets.UserTarget) for "
+                                      "larger ones" % dim)
+        if mass_f64:
+            raise NotImplementedError("a density given as a torch / Python callable runs with float32 diagonal mass matrices; "
+                                      "give it as a device functor (targets.UserTarget) for dtype='float64'")
+    if sdot is None:
+        sdot = DEFAULT_SDOT
+    if sdot == "auto":   # float32 start-energy rounding of the host's numpy (see _blas_probe.py)
+        from ._blas_probe import detect_sdot_mode
+
+        sdot = detect_sdot_mode()
+    cfg.start_energy_sdot = {"native": _abi.SDOT_NATIVE, "skylakex": _abi.SDOT_OPENBLAS_SKYLAKEX,
+                             "haswell": _abi.SDOT_OPENBLAS_HASWELL}.get(sdot, sdot)
+    return cfg, mass_f64
+
+
 class Engine:
     def __init__(self, target, chains, kind="nuts", potential="diag_adapt", device=0, lib_path=None,
                  target_accept=0.8, Emax=1000.0, adapt_step_size=True, step_scale=0.25, gamma=0.05, k=0.75,
@@ -265,65 +333,14 @@ class Engine:
         self.chains = int(chains)
         self.dim = int(target.d)
         self.kind = kind
-        cfg = _abi.Config()
-        self._lib.lmc_config_defaults(C.byref(cfg), self.chains, self.dim)
-        cfg.device = int(device)
-        cfg.kind = {"nuts": _abi.KIND_NUTS, "hmc": _abi.KIND_HMC}[kind]
-        cfg.target_family = int(target.family)
-        cfg.potential = {"diag_adapt": _abi.POT_DIAG_ADAPT, "diag": _abi.POT_DIAG, "full": _abi.POT_FULL,
-                         "full_inv": _abi.POT_FULL_INV, "full_adapt": _abi.POT_FULL_ADAPT, "full_f64": _abi.POT_FULL_F64}[potential]
         self.potential = potential
-        cfg.adapt_step_size = int(bool(adapt_step_size))
-        cfg.target_accept = float(target_accept)
-        cfg.emax = float(Emax)
-        cfg.step_scale = float(step_scale)
-        cfg.gamma = float(gamma)
-        cfg.k = float(k)
-        cfg.t0 = float(t0)
-        cfg.max_treedepth = int(max_treedepth)
-        cfg.early_max_treedepth = int(early_max_treedepth)
-        cfg.path_length = float(path_length)
-        cfg.max_steps = int(max_steps)
-        cfg.adaptation_window = int(adaptation_window)
-        cfg.adaptation_window_multiplier = float(adaptation_window_multiplier)
-        cfg.lds_levels = int(lds_levels)
-        # include/lmc_hip.h: LMC_LDS_PLAN_* (results do not depend on it; pinned values are for A/B runs and parity tests). Like
-        # the lmc_tuning knobs, the variable the LIBRARY used to read (LMC_LDS_PLAN=0 / 1) is still honoured -- by the host, and
-        # only when the caller left the choice open (tools/ab_lds_plan.sh, tools/sample_path_rate.py)
-        if lds_plan in ("auto", None):
-            import os
-
-            lds_plan = {"0": 0, "1": 1}.get(os.environ.get("LMC_LDS_PLAN", ""), "auto")
-        cfg.lds_plan = {"auto": _abi.LDS_PLAN_AUTO, None: _abi.LDS_PLAN_AUTO, 0: _abi.LDS_PLAN_SHALLOW, "shallow": _abi.LDS_PLAN_SHALLOW,
-                        1: _abi.LDS_PLAN_DEEP, "deep": _abi.LDS_PLAN_DEEP}[lds_plan]
-        for field, value in (tuning_from_env() if tuning is None else dict(tuning)).items():   # struct lmc_tuning: test / A-B knobs
-            setattr(cfg.tuning, field, int(value))
-        if cfg.tuning.sub_blocks == 0 and hw_queue_cap() is not None:   # left open: at most one sub-block per hardware queue
-            cfg.tuning.sub_blocks = -hw_queue_cap()
-        cfg.rng_mode = {"numpy": _abi.RNG_NUMPY, "philox": _abi.RNG_PHILOX, "counter": _abi.RNG_COUNTER}[rng]   # include/lmc_hip.h: LMC_RNG_*
         self.rng = rng
-        # QuadPotentialDiagAdapt(dtype=...) (quadpotential.py:159,175-184); float64 runs in the general kernels
-        # QuadPotentialFullAdapt(dtype=...) (quadpotential.py:484,497-509) likewise: float64 covariance, factor and momentum
-        self.mass_f64 = np.dtype(mass_dtype) == np.float64 and potential in ("diag_adapt", "diag", "full_adapt")
-        cfg.mass_f64 = int(self.mass_f64)
-        if cfg.target_family == _abi.TARGET_EXTERNAL:
-            # a density evaluated by the caller (a torch / Python callable) is driven by the tick kernels, which exist for the
-            # fused shapes and for float32 diagonals beyond them (include/lmc_hip.h: "Which kernels an engine runs")
-            if potential not in ("diag_adapt", "diag") and self.dim > 256:
-                raise NotImplementedError("a density given as a torch / Python callable runs with dense mass matrices up to "
-                                          "model_ndim = 256 (got %d); give it as a device functor (targets.UserTarget) for "
-                                          "larger ones" % self.dim)
-            if self.mass_f64:
-                raise NotImplementedError("a density given as a torch / Python callable runs with float32 diagonal mass matrices; "
-                                          "give it as a device functor (targets.UserTarget) for dtype='float64'")
-        if sdot is None:
-            sdot = DEFAULT_SDOT
-        if sdot == "auto":   # float32 start-energy rounding of the host's numpy (see _blas_probe.py)
-            from ._blas_probe import detect_sdot_mode
-
-            sdot = detect_sdot_mode()
-        cfg.start_energy_sdot = {"native": _abi.SDOT_NATIVE, "skylakex": _abi.SDOT_OPENBLAS_SKYLAKEX,
-                                 "haswell": _abi.SDOT_OPENBLAS_HASWELL}.get(sdot, sdot)
+        cfg, self.mass_f64 = engine_config(
+            self._lib, target, self.chains, kind=kind, potential=potential, device=device, target_accept=target_accept, Emax=Emax,
+            adapt_step_size=adapt_step_size, step_scale=step_scale, gamma=gamma, k=k, t0=t0, path_length=path_length,
+            max_treedepth=max_treedepth, early_max_treedepth=early_max_treedepth, max_steps=max_steps,
+            adaptation_window=adaptation_window, adaptation_window_multiplier=adaptation_window_multiplier, lds_levels=lds_levels,
+            sdot=sdot, rng=rng, mass_dtype=mass_dtype, lds_plan=lds_plan, tuning=tuning)
         self.cfg = cfg
         h = C.c_void_p()
         self._check(self._lib.lmc_engine_create(C.byref(cfg), C.byref(h)), handle=None)

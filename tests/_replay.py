@@ -28,11 +28,14 @@ _DENSE_KEYS = ("cov", "chol", "fore_mean", "fore_raw_cov", "fore_n", "back_mean"
 
 
 # ---- 1. the oracle half -------------------------------------------------------------------------------------------------
-def chain_iterations(ostep, tune, n):
+def chain_iterations(ostep, tune, n, after_reset=None):
     """The chain driver's switching around ``n`` iterations of ``ostep`` (sampling.py:481-521 of the reference): yields i
-    with the step ready to take iteration i. The caller takes it."""
+    with the step ready to take iteration i. The caller takes it. ``after_reset(ostep)`` is called once, right after
+    reset_tuning() and before the first iteration: a chain that starts from a state no short chain reaches."""
     ostep.tune = bool(tune)
     ostep.reset_tuning()
+    if after_reset is not None:
+        after_reset(ostep)
     for i in range(n):
         if i == 0:
             ostep.iter_count = 0
@@ -41,15 +44,16 @@ def chain_iterations(ostep, tune, n):
         yield i
 
 
-def record_chain(ostep, start, rng, tune, draws):
+def record_chain(ostep, start, rng, tune, draws, after_reset=None):
     """Run one oracle chain on ``rng`` (np.random.RandomState(seed), or _counter_model.CounterRng); return (snaps, outs) per
-    iteration. An output carries all three oracle margins; which of them count for skipping is the rules' business."""
+    iteration. An output carries all three oracle margins; which of them count for skipping is the rules' business.
+    ``after_reset``: chain_iterations' hook."""
     from oracle import lmc_oracle as orc
 
     has_state = hasattr(rng, "get_state")
     q = np.array(start, dtype="d")
     snaps, outs = [], []
-    for _i in chain_iterations(ostep, tune, tune + draws):
+    for _i in chain_iterations(ostep, tune, tune + draws, after_reset):
         pot, ad = ostep.pot, ostep.adapt
         snap = dict(q=q.copy(), tune=ostep.tune, iter_count=ostep.iter_count, log_step=float(np.ravel(ad.log_step)[0]),
                     log_bar=float(np.ravel(ad.log_bar)[0]), hbar=float(np.ravel(ad.hbar)[0]), da_count=ad.count,

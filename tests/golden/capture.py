@@ -205,31 +205,32 @@ def capture_adapt():
 # ---------------------------------------------------------------------------------------
 # 4/5. end-to-end sample() runs (sequential path)
 # ---------------------------------------------------------------------------------------
-def capture_e2e(only=None):
-    runs = [
-        # name, family, d, kind, chains, tune, draws, kwargs
-        ("e2e_hmc_c1", "std_normal", 10, "hmc", 4, 300, 200, {"path_length": 2.0}),
-        ("e2e_nuts_std64", "std_normal", 64, "nuts", 2, 250, 150, {}),
-        ("e2e_nuts_std128", "std_normal", 128, "nuts", 2, 110, 20, {}),
-        ("e2e_nuts_ar1_16", "ar1", 16, "nuts", 4, 250, 150, {}),
-        ("e2e_nuts_funnel8", "funnel", 8, "nuts", 4, 250, 150, {"max_treedepth": 12}),
-        ("e2e_nuts_diag50", "diag_gaussian", 50, "nuts", 2, 250, 100, {}),
-        ("e2e_nuts_normal1d", "normal1d", 1, "nuts", 2, 120, 80, {}),
-        # the benchmarked instantiation (BASELINE config C3's shape: AR(1) at d = 128, two elements per lane)
-        ("e2e_nuts_ar1_128", "ar1", 128, "nuts", 2, 250, 50, {}),
-        # round 6: the exact instantiations of BASELINE configs C5 and C4 -- run_kernel<4, 1, FunnelTarget> (d = 256, depth 12)
-        # and run_kernel<4, 4, DiagGaussianTarget> (d = 1000, a team of four wavefronts per chain)
-        ("e2e_nuts_funnel256", "funnel", 256, "nuts", 2, 60, 20, {"max_treedepth": 12}),
-        ("e2e_nuts_diag1000", "diag_gaussian", 1000, "nuts", 2, 60, 20, {}),
-    ]
-    for name, fam, d, kind, chains, tune, draws, kw in runs:
+E2E_RUNS = [
+    # name, family, d, kind, chains, tune, draws, kwargs
+    ("e2e_hmc_c1", "std_normal", 10, "hmc", 4, 300, 200, {"path_length": 2.0}),
+    ("e2e_nuts_std64", "std_normal", 64, "nuts", 2, 250, 150, {}),
+    ("e2e_nuts_std128", "std_normal", 128, "nuts", 2, 110, 20, {}),
+    ("e2e_nuts_ar1_16", "ar1", 16, "nuts", 4, 250, 150, {}),
+    ("e2e_nuts_funnel8", "funnel", 8, "nuts", 4, 250, 150, {"max_treedepth": 12}),
+    ("e2e_nuts_diag50", "diag_gaussian", 50, "nuts", 2, 250, 100, {}),
+    ("e2e_nuts_normal1d", "normal1d", 1, "nuts", 2, 120, 80, {}),
+    # the benchmarked instantiation (BASELINE config C3's shape: AR(1) at d = 128, two elements per lane)
+    ("e2e_nuts_ar1_128", "ar1", 128, "nuts", 2, 250, 50, {}),
+    # round 6: the exact instantiations of BASELINE configs C5 and C4 -- run_kernel<4, 1, FunnelTarget> (d = 256, depth 12)
+    # and run_kernel<4, 4, DiagGaussianTarget> (d = 1000, a team of four wavefronts per chain)
+    ("e2e_nuts_funnel256", "funnel", 256, "nuts", 2, 60, 20, {"max_treedepth": 12}),
+    ("e2e_nuts_diag1000", "diag_gaussian", 1000, "nuts", 2, 60, 20, {}),
+]
+
+def capture_e2e(only=None, runs=None, seed=SEED):
+    for name, fam, d, kind, chains, tune, draws, kw in (E2E_RUNS if runs is None else runs):
         if only and name not in only:
             continue
         f = targets.make(fam, d)
         if kind == "hmc":
             step = ref.HamiltonianMC(f, d, **kw)
             trace, stats = ref.sample(f, d, draws=draws, tune=tune, step=step, chains=chains, cores=1,
-                                      progressbar=False, random_seed=SEED, discard_tuned_samples=False)
+                                      progressbar=False, random_seed=seed, discard_tuned_samples=False)
         else:
             # the plain API call; init_nuts is wrapped only to get hold of the step object it builds
             import littlemcmc.sampling as ref_sampling
@@ -244,18 +245,18 @@ def capture_e2e(only=None):
             ref_sampling.init_nuts = spy
             try:
                 trace, stats = ref.sample(f, d, draws=draws, tune=tune, chains=chains, cores=1,
-                                          progressbar=False, random_seed=SEED,
+                                          progressbar=False, random_seed=seed,
                                           discard_tuned_samples=False, **kw)
             finally:
                 ref_sampling.init_nuts = orig
             step = made["step"]
-        np.random.seed(SEED)
+        np.random.seed(seed)
         seeds = np.array([np.random.randint(2 ** 30) for _ in range(chains)])
         np.random.seed(int(seeds[0]))
         jitter = 2 * np.random.rand(d) - 1
         arrays = dict(
             family=np.array(fam), kind=np.array(kind), d=np.array(d), chains=np.array(chains),
-            tune=np.array(tune), draws=np.array(draws), random_seed=np.array(SEED), seeds=seeds,
+            tune=np.array(tune), draws=np.array(draws), random_seed=np.array(seed), seeds=seeds,
             start=jitter, params=f.params(), trace=trace,
             kw_names=np.array(list(kw.keys()), dtype="U32"), kw_vals=np.array(list(kw.values()), dtype="d"),
             final_var=np.asarray(step.potential._var),
@@ -272,6 +273,16 @@ def capture_e2e(only=None):
 # ---------------------------------------------------------------------------------------
 # 6. seed derivation
 # ---------------------------------------------------------------------------------------
+def capture_settings():
+    """Sampler settings off their defaults: the captured cases of tests/_settings_cases.py (the one table of them; what each
+    chain does with its settings is asserted where the cases are replayed, tests/test_gpu_settings_replay.py). Two chains
+    each, so every golden has a chain on seeds[1] as well. Booleans travel as 0.0 / 1.0 in kw_vals, like every other value."""
+    from tests._settings_cases import CASES, GOLDEN, SEED as settings_seed
+
+    capture_e2e(runs=[("e2e_set_" + n, c.family, c.d, c.kind, 2, c.tune, c.draws, dict(c.kw)) for n, c in CASES.items() if n in GOLDEN],
+                seed=settings_seed)
+
+
 def capture_seeds():
     out = {}
     for chains in (2, 4, 64):
@@ -709,7 +720,7 @@ def capture_full_adapt_two_chains():
 
 
 CAPTURES = {"full_adapt_two_chains": capture_full_adapt_two_chains, "leapfrog": capture_leapfrog, "transitions": capture_transitions, "adapt": capture_adapt,
-            "e2e": capture_e2e, "seeds": capture_seeds, "dense_units": capture_dense_units,
+            "e2e": capture_e2e, "settings": capture_settings, "seeds": capture_seeds, "dense_units": capture_dense_units,
             "dense_adapt": capture_dense_adapt, "dense_e2e": capture_dense_e2e, "dense_full64": capture_dense_full64,
             "diag_window_multiplier": capture_diag_window_multiplier, "step_rand": capture_step_rand,
             "diag_float64": capture_diag_float64, "full_adapt_float64": capture_full_adapt_float64, "step_rand_callable": capture_step_rand_callable, "wide": capture_wide}

@@ -10,6 +10,7 @@ from littlemcmc_amd import targets as T
 from oracle import lmc_oracle as orc
 from oracle import targets as OT
 from tests._gpu_util import FRAGILE, assert_chain_matches, device_target, kwargs_from
+from tests._settings_cases import GOLDEN
 
 pytestmark = pytest.mark.gpu
 
@@ -89,6 +90,9 @@ E2E = ["e2e_hmc_c1", "e2e_nuts_std64", "e2e_nuts_std128", "e2e_nuts_ar1_16", "e2
        # round 6: reference-held chains at the exact instantiations of BASELINE's C5 and C4 -- run_kernel<4, 1, FunnelTarget>
        # (d = 256, max_treedepth 12) and run_kernel<4, 4, DiagGaussianTarget> (d = 1000, four wavefronts per chain)
        "e2e_nuts_funnel256", "e2e_nuts_diag1000"]
+# sampler settings off their defaults (tests/_settings_cases.py; tests/test_gpu_settings_replay.py replays them per kernel family)
+E2E_SETTINGS = ["e2e_set_" + case for case in GOLDEN]
+E2E = E2E + E2E_SETTINGS
 
 
 @pytest.mark.parametrize("name", E2E)
@@ -133,7 +137,12 @@ def test_e2e_golden_through_sample_api(golden_dir, name):
     # captured chains) minus ~20 % for hosts whose float32 BLAS dot rounds differently from the capture host's.
     floors = {"e2e_hmc_c1": 1300, "e2e_nuts_std64": 56, "e2e_nuts_std128": 30, "e2e_nuts_ar1_16": 120,
               "e2e_nuts_funnel8": 125, "e2e_nuts_diag50": 84, "e2e_nuts_normal1d": 400, "e2e_nuts_ar1_128": 25,
-              "e2e_nuts_funnel256": 16, "e2e_nuts_diag1000": 16}
+              "e2e_nuts_funnel256": 16, "e2e_nuts_diag1000": 16,
+              # the settings goldens, two chains each, measured on MI355X: da_params 100 of 100, low_accept 82 of 100,
+              # emax_funnel 105 of 160, depth_caps 120 of 120, fixed_step 80 of 80, hmc_caps 100 of 100, hmc_emax 74 of 140;
+              # the same 20 % off
+              "e2e_set_da_params": 80, "e2e_set_low_accept": 65, "e2e_set_emax_funnel": 84, "e2e_set_depth_caps": 96,
+              "e2e_set_fixed_step": 64, "e2e_set_hmc_caps": 80, "e2e_set_hmc_emax": 59}
     assert verified >= min(floors[name], chains * (tune + draws)), "%s: only %d iterations verified" % (name, verified)
 
 
@@ -147,7 +156,8 @@ def test_every_iteration_of_the_golden_runs(golden_dir, name):
     positions / energies / adaptation state to 1e-10."""
     from tests._gpu_util import replay_golden_run
 
-    total_checked, total_fragile, total = replay_golden_run(golden_dir, name)
+    # the settings goldens also require that the oracle on this host IS the captured chain (and so compare its diverging flags)
+    total_checked, total_fragile, total = replay_golden_run(golden_dir, name, require_same=name in E2E_SETTINGS)
     print("%s: replay checked %d of %d iterations, %d fragile" % (name, total_checked, total, total_fragile))
     # measured on MI355X (round 3): every iteration of every golden checked, none fragile
     assert total_checked >= total - 2, (total_checked, total_fragile)

@@ -120,7 +120,10 @@ def test_seed_derivation_golden(golden_dir):
 
 
 E2E = ["e2e_hmc_c1", "e2e_nuts_std64", "e2e_nuts_std128", "e2e_nuts_ar1_16", "e2e_nuts_funnel8",
-       "e2e_nuts_diag50", "e2e_nuts_normal1d", "e2e_nuts_ar1_128", "e2e_nuts_funnel256", "e2e_nuts_diag1000"]
+       "e2e_nuts_diag50", "e2e_nuts_normal1d", "e2e_nuts_ar1_128", "e2e_nuts_funnel256", "e2e_nuts_diag1000",
+       # sampler settings off their defaults (capture.py settings; tests/_settings_cases.py)
+       "e2e_set_da_params", "e2e_set_low_accept", "e2e_set_emax_funnel", "e2e_set_depth_caps", "e2e_set_fixed_step",
+       "e2e_set_hmc_caps", "e2e_set_hmc_emax"]
 
 
 @pytest.mark.parametrize("name", E2E)
@@ -132,12 +135,15 @@ def test_e2e_golden(golden_dir, name):
         f = targets.DiagGaussian(g["params"])
     else:
         f = targets.make(str(g["family"]), d)
-    step = None
+    seeds = orc.derive_seeds(int(g["random_seed"]), chains)
+    np.testing.assert_array_equal(seeds, g["seeds"])
+    np.testing.assert_array_equal(orc.jitter_start(seeds[0], d), g["start"])
     if str(g["kind"]) == "hmc":
         step = orc.Step(f, d, kind="hmc", **kw)
-        kw = {}
+    else:
+        step = orc.init_nuts(f, d, seeds=seeds, **kw)[1]   # what sample() builds itself; held here to read its final state
     trace, stats = orc.sample(f, d, draws=draws, tune=tune, step=step, chains=chains,
-                              random_seed=int(g["random_seed"]), discard_tuned_samples=False, **kw)
+                              random_seed=int(g["random_seed"]), discard_tuned_samples=False)
     assert trace.shape == (chains, tune + draws, d) == g["trace"].shape
     for name_ in stats:
         want = g["stat_" + name_]
@@ -148,6 +154,19 @@ def test_e2e_golden(golden_dir, name):
         else:
             np.testing.assert_allclose(stats[name_], want, rtol=RTOL, atol=1e-12, err_msg=name_)
     np.testing.assert_allclose(trace, g["trace"], rtol=RTOL, atol=1e-300)
+    # the state the one step object is left with after the last chain
+    ad = step.adapt
+    np.testing.assert_allclose([float(np.ravel(x)[0]) for x in (ad.log_step, ad.log_bar, ad.hbar, ad.count)], g["final_da"],
+                               rtol=RTOL, atol=1e-12)
+    np.testing.assert_allclose(np.asarray(step.pot.var, dtype="d"), g["final_var"], rtol=RTOL)
+    assert step.pot.n_samples == int(g["final_n_samples"])
+    if name.startswith("e2e_set_"):
+        from tests._settings_cases import assert_the_case_does_what_it_is_for
+
+        # chain 0 is the chain the cases were chosen on and the one replayed per kernel family (tests/test_gpu_settings_replay.py)
+        # -- asserted on the REFERENCE's own statistics here
+        assert_the_case_does_what_it_is_for(name[len("e2e_set_"):],
+                                            {k[len("stat_"):]: g[k][0, :, 0] for k in g.files if k.startswith("stat_")}, tune)
 
 
 def test_diag_adapt_growing_window_golden(golden_dir):

@@ -104,3 +104,40 @@ def test_the_divergence_margin_skips_under_the_dense_rule_only():
     ran.iterations[0] = got
     assert assert_replay(ran, [nxt], [want], RULES["diag"], "div margin")[:2] == (1, 0)
     assert assert_replay(ran, [nxt], [want], RULES["diag"], "div margin", skip=lambda i: True)[:2] == (0, 1)
+
+
+def test_the_after_reset_hook_runs_once_between_the_reset_and_the_first_iteration():
+    """record_chain / chain_iterations(after_reset=...): what the hook sets survives reset_tuning() and is what the first
+    snapshot carries -- a chain that starts where no short chain gets to (a dual-averaging count of 16 380)."""
+    from oracle import lmc_oracle as orc
+    from oracle import targets as OT
+    from tests._replay import chain_iterations, record_chain
+
+    d, seed = 3, 77
+    calls = []
+
+    def late(step):
+        assert step.tune and step.adapt.count == 1 and step.adapt.hbar == 0.0    # reset_tuning() has already run
+        calls.append(step)
+        step.adapt.count = 16380
+
+    def chain(hook):
+        start, ostep = orc.init_nuts(OT.make("std_normal", d), d, seeds=[seed], k=0.6)
+        ostep.adapt.count = 5                                                      # (a left-over the reset clears)
+        return ostep, record_chain(ostep, start, np.random.RandomState(seed), 4, 2, after_reset=hook)
+
+    ostep, (snaps, outs) = chain(late)
+    assert calls == [ostep]
+    assert [s["da_count"] for s in snaps] == [16380, 16381, 16382, 16383, 16384, 16384]   # draws do not count
+    assert [s["tune"] for s in snaps] == [True] * 4 + [False] * 2 and [s["iter_count"] for s in snaps] == list(range(6))
+    _, (plain, plain_outs) = chain(None)
+    assert [s["da_count"] for s in plain] == [1, 2, 3, 4, 5, 5]
+    np.testing.assert_array_equal(plain[0]["q"], snaps[0]["q"])
+    np.testing.assert_array_equal(plain_outs[0]["q"], outs[0]["q"])            # the first transition does not read the count
+    assert plain[1]["log_bar"] != snaps[1]["log_bar"]                            # ... its update does: count ** -k
+    w = 1.0 / (16380 + 10)
+    assert snaps[1]["hbar"] == pytest.approx(w * (0.8 - outs[0]["stats"]["mean_tree_accept"]), rel=1e-14)
+    # chain_iterations on its own: once, before the first yield
+    calls.clear()
+    seen = [(i, len(calls)) for i in chain_iterations(ostep, 2, 3, after_reset=late)]
+    assert seen == [(0, 1), (1, 1), (2, 1)]
