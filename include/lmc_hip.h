@@ -804,6 +804,30 @@ int lmc_glm_linpred(const double* x, int64_t chains, int64_t draws_stride, int32
                     const double* rows, int64_t row_len, int64_t n_rows, int64_t first_chain, int64_t chains_per_group,
                     int64_t ob0, int64_t ob1, double* eta, double* stats, void* stream);
 
+/* ---- posterior co-moments per posterior from the draws in HBM (additive within ABI 9; littlemcmc_amd/diagnostics.py:
+ * cross_moments, covariance, contrasts) -------------------------------------------------------------------------------------
+ * x, chains, draws_stride, dim, t0, n, first_chain, chains_per_group: the trace block, sub-series and groups of
+ * lmc_diag_chain_stats_grouped -- the block touches groups g0 .. g1. For each touched group, over the n_g rows of that group
+ * that lie in the block (its chains that are present x the draws [t0, t0 + n)), the call writes (DEVICE, overwritten)
+ *   n_out    [g1 - g0 + 1]            n_g as a double
+ *   mean_out [g1 - g0 + 1][dim]       the mean row
+ *   m2_out   [g1 - g0 + 1][dim][dim]  sum_rows (x - mean)(x - mean)^T, row-major, full and exactly symmetric (the lower
+ *                                     triangle is computed and mirrored)
+ * Arithmetic (csrc/lmc_cross.hip): shift = the column mean of the group's present rows (per-workgroup column sums, added in
+ * workgroup order); s = sum (x - shift) and S = sum (x - shift)(x - shift)^T on v_mfma_f64_16x16x4_f64, per-workgroup
+ * partials added in workgroup order; mean = shift + s / n_g, m2 = S - s s^T / n_g. No floating-point atomics, and the split
+ * of the rows over workgroups is a function of the shapes alone: the same draws give the same bits. n = 1 is allowed (m2 is
+ * all zeros, mean the draw). Two blocks a, b merge by Chan's rule for matrices, m2 = m2a + m2b + (mb - ma)(mb - ma)^T na nb /
+ * n, a block of count 0 skipped by its count (diagnostics.merge_cross_moments).
+ * A NaN or +-inf in coordinate j of some draw makes mean[j] and row and column j of m2 non-finite; every other entry keeps
+ * the bits it has without it (column i's shift reads column i only, and every tile entry is its own dot product).
+ * Refused with LMC_ERR_INVALID before any HIP call: what lmc_diag_chain_stats_grouped refuses of the trace view and the
+ * grouping (its n >= 2 aside); NULL n_out, mean_out or m2_out; dim > LMC_CROSS_MAX_DIM. */
+#define LMC_CROSS_MAX_DIM 512
+int lmc_diag_cross_moments(const double* x, int64_t chains, int64_t draws_stride, int32_t dim, int64_t t0, int64_t n,
+                           int64_t first_chain, int64_t chains_per_group, double* n_out, double* mean_out, double* m2_out,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif

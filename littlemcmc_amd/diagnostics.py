@@ -23,7 +23,11 @@ the test oracle's restatement of the kernel's block (oracle/diagnostics_oracle.p
 
 Posterior quantiles, equal-tailed credible intervals and tail-ESS (``order_statistics``, ``quantiles``, ``intervals``,
 ``tail_ess``, at the end of this module) follow the same rule with an integer statistic: a radix select whose passes are
-histograms of key digits from ``lmc_select_digit_counts`` (csrc/lmc_select.hip), exact and additive over chains and GPUs."""
+histograms of key digits from ``lmc_select_digit_counts`` (csrc/lmc_select.hip), exact and additive over chains and GPUs.
+
+Posterior covariance and correlation per posterior (``cross_moments``, ``covariance``, ``contrasts``, after them) are one
+contraction over the (chain, draw) rows of every group on the FP64 matrix cores, ``lmc_diag_cross_moments``
+(csrc/lmc_cross.hip); blocks merge by Chan's rule for matrices (``merge_cross_moments``)."""
 import collections
 import ctypes
 import math
@@ -755,3 +759,125 @@ def tail_ess(x, probs=(0.05, 0.95), split=True, chains_per_group=None, chunk_dim
     if chains_per_group is not None:
         out.update(groups=G, ess_tail_min=best.min(dim=-1).values)
     return out
+
+
+# ---- posterior covariance and correlation per posterior: the co-moment matrix of the draws in place ------------------------
+# One contraction over the (chain, draw) rows of every group on the FP64 matrix cores (include/lmc_hip.h:
+# lmc_diag_cross_moments, csrc/lmc_cross.hip) -> n[G], mean[G, d], m2[G, d, d]; blocks merge by Chan's rule for matrices.
+def _hip_cross_moments(x, first_chain, per):
+    """One call of lmc_diag_cross_moments over x[chains, draws, d] (a ROCm tensor), x's chain 0 being chain ``first_chain`` of
+    the job: -> dict(n[groups touched], mean[.., d], m2[.., d, d]) float64 on x's device."""
+    from . import _abi
+
+    c, _n, d = x.shape
+    if d > _abi.CROSS_MAX_DIM:
+        raise ValueError("cross_moments: d = %d is beyond the %d dimensions of lmc_diag_cross_moments" % (d, _abi.CROSS_MAX_DIM))
+    touched = _touched(first_chain, c, per)[1]
+    out = {"n": torch.empty((touched,), dtype=torch.float64, device=x.device),
+           "mean": torch.empty((touched, d), dtype=torch.float64, device=x.device),
+           "m2": torch.empty((touched, d, d), dtype=torch.float64, device=x.device)}
+    _call_trace_kernel("lmc_diag_cross_moments", x, int(first_chain), int(per), out["n"], out["mean"], out["m2"])
+    return out
+
+
+def merge_cross_moments(a, b):
+    """Two results dict(n[G], mean[G, d], m2[G, d, d]) over disjoint sets of draws of the same groups -> the result over their
+    union, by Chan's rule for matrices:
+
+        n = na + nb,  mean = ma + (mb - ma) nb / n,  m2 = m2a + m2b + (mb - ma)(mb - ma)^T na nb / n
+
+    A side of count 0 is skipped BY ITS COUNT: the other side comes through bit for bit, whatever the empty side holds, so
+    zeros are the identity. The outer product of one vector with itself is symmetric bit for bit, so symmetric sides merge to
+    a symmetric matrix."""
+    na, nb = a["n"], b["n"]
+    n = na + nb
+    delta = b["mean"] - a["mean"]
+    mean = a["mean"] + delta * (nb / n).unsqueeze(-1)
+    m2 = a["m2"] + b["m2"] + delta.unsqueeze(-1) * delta.unsqueeze(-2) * (na * nb / n).unsqueeze(-1).unsqueeze(-1)
+    only_a, only_b = nb == 0, na == 0
+    pick = lambda ta, tb, both, k: torch.where(only_a.reshape(only_a.shape + (1,) * k), ta,
+                                               torch.where(only_b.reshape(only_b.shape + (1,) * k), tb, both))
+    return {"n": pick(na, nb, n, 0), "mean": pick(a["mean"], b["mean"], mean, 1), "m2": pick(a["m2"], b["m2"], m2, 2)}
+
+
+def _pack_cross(m):
+    """dict(n[g], mean[g, d], m2[g, d, d]) as one tensor [g, 1 + d + d d] (what _fan_out folds), and back."""
+    g = m["n"].shape[0]
+    return torch.cat([m["n"].reshape(g, 1), m["mean"], m["m2"].reshape(g, -1)], dim=1)
+
+
+def _unpack_cross(t, d):
+    return {"n": t[:, 0], "mean": t[:, 1:1 + d], "m2": t[:, 1 + d:].reshape(t.shape[0], d, d)}
+
+
+def cross_moments(x, chains_per_group=None, first_chain=0, moments_fn=None, target=None):
+    """Count, mean and co-moment matrix of the draws in HBM per posterior -> dict(n[G], mean[G, d], m2[G, d, d]) on the first
+    block's device, ``m2 = sum over the group's (chain, draw) rows of (x - mean)(x - mean)^T``, exactly symmetric. One
+    posterior per ``chains_per_group`` consecutive chains of the job (default: ``target.group_size`` of a ``targets.Batched``,
+    else one group of all chains -- and then, without a Batched target, the leading axis is dropped, as ``summarize`` does).
+    x is one tensor [chains, draws, d] whose chain 0 is chain ``first_chain`` of the job -- a first or last group that lies only
+    partly in x gets the moments of its chains that are present -- or the list of per-GPU blocks of one job in job order: every
+    block is taken on its own device and the parts are merged in job order (``merge_cross_moments``), so a group may straddle
+    blocks. d <= 512. ``moments_fn(x, first_chain, per) -> dict`` replaces the HIP call (tests of this logic only); without it
+    a CPU tensor raises HipLibraryError. Not with an active process group."""
+    job = _trace_job(x, chains_per_group, first_chain, target=target, allow_first_chain=True)
+    fn = _hip_cross_moments if moments_fn is None else moments_fn
+    d = job.d
+    if len(job.held) == 1:
+        out = fn(job.held[0], job.firsts[0], job.per)
+        out = {k: out[k].to(job.device) for k in ("n", "mean", "m2")}
+    else:
+        out = _unpack_cross(_fan_out(job, job.g0, job.g0 + job.groups, lambda b, f: _pack_cross(fn(b, f, job.per)),
+                                     lambda a, b: _pack_cross(merge_cross_moments(_unpack_cross(a, d), _unpack_cross(b, d)))), d)
+    if chains_per_group is None and not hasattr(target, "group_size"):
+        out = {k: v[0] for k, v in out.items()}
+    return out
+
+
+def _cov_of(moments, ddof):
+    """cov = m2 / (n - ddof), NaN where n - ddof <= 0 (numpy.cov warns and divides by zero there; here it is NaN throughout)."""
+    dof = moments["n"] - float(ddof)
+    dof = torch.where(dof > 0, dof, torch.full_like(dof, float("nan")))
+    return moments["m2"] / dof.unsqueeze(-1).unsqueeze(-1)
+
+
+def covariance(x, chains_per_group=None, ddof=1, **kw):
+    """Posterior covariance and correlation per posterior from the draws in HBM -> dict(n, mean, cov, sd, corr, m2):
+    ``cov = m2 / (n - ddof)`` ([G, d, d]; NaN where n - ddof <= 0, like numpy.cov), ``sd = sqrt(diag cov)``, ``corr_ij = m2_ij /
+    sqrt(m2_ii m2_jj)`` clipped to [-1, 1] as numpy.corrcoef does, exactly 1 on the diagonal, and NaN in the row and column of
+    a coordinate whose variance is 0 or not finite. ``**kw`` goes to ``cross_moments`` (``first_chain``, ``target``,
+    ``moments_fn``); the leading axis is dropped as there.
+
+    This is the SAMPLE covariance of autocorrelated draws, all chains of a posterior pooled. It estimates the posterior
+    covariance; it says nothing about the Monte Carlo error of that estimate (see ``summarize`` for the ESS of the means)."""
+    mo = cross_moments(x, chains_per_group=chains_per_group, **kw)
+    cov = _cov_of(mo, ddof)
+    var = torch.diagonal(mo["m2"], dim1=-2, dim2=-1)
+    root = torch.sqrt(torch.where(torch.isfinite(var) & (var > 0), var, torch.full_like(var, float("nan"))))
+    corr = (mo["m2"] / root.unsqueeze(-1) / root.unsqueeze(-2)).clamp(-1.0, 1.0)
+    eye = torch.eye(corr.shape[-1], dtype=torch.bool, device=corr.device)
+    corr = torch.where(eye & ~torch.isnan(corr), torch.ones_like(corr), corr)
+    return {"n": mo["n"], "mean": mo["mean"], "cov": cov, "sd": torch.sqrt(torch.diagonal(cov, dim1=-2, dim2=-1)), "corr": corr,
+            "m2": mo["m2"]}
+
+
+def contrasts(moments, L, ddof=1):
+    """Posterior mean, sd and covariance of the linear combinations ``L q`` from a ``cross_moments`` / ``covariance`` result ->
+    dict(mean[G, k], sd[G, k], cov[G, k, k]); ``L`` is [k, d] (the same contrasts for every posterior) or [G, k, d]. The
+    covariance is the result's own ``cov`` if it has one, else ``m2 / (n - ddof)``. An ungrouped result ([d], [d, d]) gives
+    [k], [k], [k, k]. Small torch matmuls on the result's device; works on CPU tensors too."""
+    mean = moments["mean"]
+    cov = moments["cov"] if "cov" in moments else _cov_of(moments, ddof)
+    L = torch.as_tensor(L, dtype=torch.float64, device=mean.device)
+    single = mean.dim() == 1
+    if single:
+        mean, cov = mean.unsqueeze(0), cov.unsqueeze(0)
+    if L.dim() == 2:
+        L = L.unsqueeze(0).expand(mean.shape[0], -1, -1)
+    if L.dim() != 3 or L.shape[0] != mean.shape[0] or L.shape[2] != mean.shape[1]:
+        raise ValueError("L must be [k, %d] or [%d, k, %d] (got %s)" % (mean.shape[1], mean.shape[0], mean.shape[1], tuple(L.shape)))
+    cm = torch.matmul(L, mean.unsqueeze(-1)).squeeze(-1)
+    cc = torch.matmul(torch.matmul(L, cov), L.transpose(1, 2))
+    cc = 0.5 * (cc + cc.transpose(1, 2))
+    out = {"mean": cm, "sd": torch.sqrt(torch.diagonal(cc, dim1=-2, dim2=-1)), "cov": cc}
+    return {k: v[0] for k, v in out.items()} if single else out

@@ -250,6 +250,19 @@ class GLM(DeviceTarget):
 
         return predictive.predict(x, self, X_new, **kw)
 
+    def covariance(self, x, **kw):
+        """``diagnostics.covariance(x, ...)``: posterior covariance, correlation and sd of the coefficients from the draws ``x`` in
+        HBM -- ``cov[d, d]``, ``corr[d, d]``, ``sd[d]``, ``mean[d]``."""
+        from . import diagnostics
+
+        return diagnostics.covariance(x, target=self, **kw)
+
+    def contrasts(self, x, L, **kw):
+        """``diagnostics.contrasts`` of ``covariance(x, ...)``: mean[k], sd[k] and cov[k, k] of the combinations ``L q``, L [k, d]."""
+        from . import diagnostics
+
+        return diagnostics.contrasts(self.covariance(x, **kw), L, ddof=kw.get("ddof", 1))
+
     def __repr__(self):
         return "GLM(%s, N=%d, d=%d)" % (self.likelihood, self.n_obs, self.d)
 
@@ -742,6 +755,20 @@ class Batched(DeviceTarget):
         from . import diagnostics
 
         return diagnostics.tail_ess(x, chains_per_group=self._per(x), **kw)
+
+    def covariance(self, x, **kw):
+        """``diagnostics.covariance`` per posterior: cov[G, d, d], corr[G, d, d], sd[G, d], mean[G, d], n[G] from the draws in
+        HBM (one tensor or the list of per-GPU blocks); ``cov[g]`` is a dense mass matrix for a rerun of posterior g."""
+        from . import diagnostics
+
+        return diagnostics.covariance(x, chains_per_group=self._per(x), **kw)
+
+    def contrasts(self, x, L, **kw):
+        """``diagnostics.contrasts`` of ``covariance(x, ...)`` per posterior: mean[G, k], sd[G, k], cov[G, k, k] of the
+        combinations ``L q``, L [k, d] (the same for every posterior) or [G, k, d]."""
+        from . import diagnostics
+
+        return diagnostics.contrasts(self.covariance(x, **kw), L, ddof=kw.get("ddof", 1))
 
     def pointwise_stats(self, x, **kw):
         """``predictive.pointwise_stats(x, self, ...)`` per posterior (GLM members): the per-observation statistics ``[G, N]``."""
