@@ -828,6 +828,59 @@ int lmc_diag_cross_moments(const double* x, int64_t chains, int64_t draws_stride
                            int64_t first_chain, int64_t chains_per_group, double* n_out, double* mean_out, double* m2_out,
                            void* stream);
 
+/* ---- replicated responses y_rep ~ p(y | q_s), GLM family (additive within ABI 9; littlemcmc_amd/predictive.py: replicate,
+ * predict_response, ppc; csrc/lmc_yrep.hpp, csrc/lmc_yrep.hip) ---------------------------------------------------------------
+ * THE STREAM. The replicated response of draw row r = t0 + t of job chain first_chain + c at observation i of the chain's row
+ * is a pure function of (seed, job chain, r, i) and of the draw's eta and mu at i (those of lmc_glm_linpred, bit for bit):
+ *   w(b) = philox4x32_10(c0 = r, c1 = i, c2 = b, c3 = 0x6c6d6379 "lmcy", k0 = seed, k1 = job chain),  b = 0, 1, ...
+ *   m_j  = (a >> 5) 2^26 + (b >> 6) with (a, b) = words (0, 1) of w(j >> 1) for even j, words (2, 3) for odd j
+ *   u_j  = m_j / 2^53 in [0, 1): the 53-bit form of the decision stream (LMC_RNG_COUNTER above)
+ * c3 keeps the counter space disjoint from "lmcm" and "lmcu". Nothing lives in memory: a value does not depend on the launch
+ * shape, the chunking, the observation-block range, the chain-block partition or the device.
+ *   bernoulli  y = (u_0 < mu) ? 1 : 0
+ *   gaussian   y = fma(sigma, z, eta), sigma = 1 / sqrt(isig2), z = Phi^-1((m_0 + 1/2) 2^-53) by Wichura's AS 241 (PPND16) in
+ *              float64: q = (m_0 - 2^52 + 1/2) 2^-53 exactly; |q| <= 0.425: the central rational in 0.180625 - q^2; otherwise
+ *              r = sqrt(-log(min(p, 1 - p))) with the minimum formed exactly as (m_0 + 1/2) 2^-53 or (2^53 - m_0 - 1/2) 2^-53,
+ *              and the rational in r - 1.6 (r <= 5) or r - 5, negated for q < 0. No word pair gives p = 0 or 1; z is finite and
+ *              antisymmetric in m_0 <-> 2^53 - 1 - m_0. No rejection, no float32.
+ *   poisson    lam = mu = exp(eta).  lam = 0: y = 0.  lam < 10, the multiplication method: prod = 1; prod *= u_j for j = 0, 1,
+ *              .. until prod <= exp(-lam); y = that j.  lam >= 10, PTRS (Hoermann 1993) as numpy's legacy generator states it:
+ *                slam = sqrt(lam), loglam = log(lam), b = 0.931 + 2.53 slam, a = -0.059 + 0.02483 b,
+ *                invalpha = 1.1239 + 1.1328 / (b - 3.4), vr = 0.9277 - 3.6224 / (b - 2);
+ *                attempt t: U = u_(2t) - 0.5, V = u_(2t+1), us = 0.5 - |U|, k = floor((2 a / us + b) U + lam + 0.43);
+ *                accept k if us >= 0.07 and V <= vr; reject if k < 0 or (us < 0.013 and V > us); otherwise accept iff
+ *                log V + log invalpha - log(a / us^2 + b) <= -lam + k loglam - lgamma(k + 1).
+ * eta NaN, mu NaN or mu = +inf give y = NaN, and so does a poisson mu > 2^52. Loops are bounded: after 64 PTRS attempts or 1024
+ * uniforms of the multiplication method y = NaN (probability below 1e-30). A count is returned as a double.
+ *
+ * lmc_glm_yrep: the arguments of lmc_glm_linpred (rows: the points to predict at, their y section NOT READ) and `seed`;
+ *   y  [chains][n][W] doubles (DEVICE), W = 64 (ob1 - ob0): y[c][t][64 (ob - ob0) + lane] is the replicated response of draw
+ *      t0 + t of chain c at observation 64 ob + lane -- the layout of lmc_glm_linpred's eta, a trace with dim = W, so its
+ *      order statistics are lmc_select_digit_counts on it. Observations i >= N (padding) hold 0.
+ * Refused with LMC_ERR_INVALID before any HIP call: what lmc_glm_linpred refuses, with `y` NULL in place of both outputs NULL.
+ *
+ * lmc_glm_yrep_stats: test statistics of every draw's replicated data set, which is never written. rows are the rows of the
+ * DATA (all N observations are read, y section included); centre[n_rows] (DEVICE) holds one number per row (the host passes
+ * the mean of the row's y). With y_rep_i the value lmc_glm_yrep writes on the same seed, bit for bit (one device function),
+ *   T  [chains][n][LMC_YREP_STATS] doubles (DEVICE), per draw over the N real observations of the chain's row g:
+ *        [0] sum_i y_rep_i   [1] sum_i (y_rep_i - centre[g])^2   [2] min_i y_rep_i   [3] max_i y_rep_i
+ *        [4] the number of y_rep_i == 0
+ *        [5] sum_i (y_rep_i - mu_i)^2 / V_i   [6] sum_i (y_i - mu_i)^2 / V_i,  V = mu (1 - mu) | mu | 1 / isig2
+ *      a trace-shaped block (dim = 7): lmc_select_digit_counts and the diagnostics read it as they read a trace.
+ * Arithmetic is plain (one rounding an operation). A lane accumulates its observations 64 ob + lane over ob ascending; one
+ * reduction over the 64 lanes per plane follows -- the balanced tree of the library's wave sum (row_shr 1, 2, 4, 8, row_bcast
+ * 15, 31), for [2] and [3] the same tree with a min / max that KEEPS a NaN. A NaN y_rep or V = 0 makes the planes it enters of
+ * that draw non-finite and touches no other draw. Bit-reproducible; the mu of a NaN eta is NaN.
+ * Refused with LMC_ERR_INVALID before any HIP call: what lmc_glm_pointwise refuses before its header copy (its `out` aside);
+ * centre or T NULL; chains * n * 7 >= 2^40. Then the header check of lmc_glm_pointwise, on the touched rows. */
+#define LMC_YREP_STATS 7
+int lmc_glm_yrep(const double* x, int64_t chains, int64_t draws_stride, int32_t dim, int64_t t0, int64_t n,
+                 const double* rows, int64_t row_len, int64_t n_rows, int64_t first_chain, int64_t chains_per_group,
+                 int64_t ob0, int64_t ob1, uint32_t seed, double* y, void* stream);
+int lmc_glm_yrep_stats(const double* x, int64_t chains, int64_t draws_stride, int32_t dim, int64_t t0, int64_t n,
+                       const double* rows, int64_t row_len, int64_t n_rows, int64_t first_chain, int64_t chains_per_group,
+                       uint32_t seed, const double* centre, double* T, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,17 +26,18 @@ __device__ __forceinline__ double grow_at(GRow base, unsigned bytes) {
     return *reinterpret_cast<GRow>(reinterpret_cast<const __attribute__((address_space(1))) char*>(base) + bytes);
 }
 
-// The contraction alone: eta[i] of the tile's draws. qt: the tile's first draw (dim doubles a draw), k <= kPredT draws of it
-// exist (wave-uniform); xt: the row's Xt section, col0 the lane's byte offset in a row of it, row_bytes = npad * 8. eta[i] for
+// The contraction alone: eta[i] of the tile's draws. qt: the tile's first draw (dim doubles a draw), k <= T draws of it
+// exist (wave-uniform; T, the tile's width, is kPredT everywhere but in yrep_stats_kernel, lmc_yrep.hip); xt: the row's Xt section, col0 the lane's byte offset in a row of it, row_bytes = npad * 8. eta[i] for
 // i >= k repeats draw k - 1. The y section of the row is not touched (lmc_linpred.hip predicts where no y is known).
+template <int T>
 __device__ __forceinline__ void glm_eta_tile(const double* qt, int k, int dim, GRow xt, unsigned col0, unsigned row_bytes,
-                                             double (&eta)[kPredT]) {
+                                             double (&eta)[T]) {
     // a tile's missing draws repeat its last one (a valid row; the callers deselect their values)
-    int qoff[kPredT];
+    int qoff[T];
 #pragma unroll
-    for (int i = 0; i < kPredT; ++i) qoff[i] = (i < k ? i : k - 1) * dim;
+    for (int i = 0; i < T; ++i) qoff[i] = (i < k ? i : k - 1) * dim;
 #pragma unroll
-    for (int i = 0; i < kPredT; ++i) eta[i] = 0.0;
+    for (int i = 0; i < T; ++i) eta[i] = 0.0;
     unsigned col = col0;
     int e0 = 0;
     for (; e0 + kPredBatch <= dim; e0 += kPredBatch) {
@@ -46,7 +47,7 @@ __device__ __forceinline__ void glm_eta_tile(const double* qt, int k, int dim, G
 #pragma unroll
         for (int j = 0; j < kPredBatch; ++j)
 #pragma unroll
-            for (int i = 0; i < kPredT; ++i) eta[i] = __builtin_fma(xv[j], qt[qoff[i] + e0 + j], eta[i]);
+            for (int i = 0; i < T; ++i) eta[i] = __builtin_fma(xv[j], qt[qoff[i] + e0 + j], eta[i]);
         col += kPredBatch * row_bytes;
     }
     if (e0 < dim) {   // the last rows: Xt is padded to 8 rows (zeros), the trace row is NOT: q[e] only for e < dim
@@ -58,7 +59,7 @@ __device__ __forceinline__ void glm_eta_tile(const double* qt, int k, int dim, G
             const bool have = e0 + j < dim;
             const int e = have ? e0 + j : dim - 1;
 #pragma unroll
-            for (int i = 0; i < kPredT; ++i) {
+            for (int i = 0; i < T; ++i) {
                 const double qv = qt[qoff[i] + e];
                 eta[i] = __builtin_fma(xv[j], have ? qv : 0.0, eta[i]);
             }
@@ -68,24 +69,25 @@ __device__ __forceinline__ void glm_eta_tile(const double* qt, int k, int dim, G
 
 // The link of a tile's eta, the functor's expressions: l[i] the pointwise log-likelihood at the lane's y = yn (constants
 // dropped), mu[i] the mean response sigmoid(eta) | exp(eta) | eta. A caller that wants mu alone passes any yn and drops l.
-__device__ __forceinline__ void glm_link_of_eta(int lik, double yn, double isig2, const double (&eta)[kPredT],
-                                                double (&l)[kPredT], double (&mu)[kPredT]) {
+template <int T>
+__device__ __forceinline__ void glm_link_of_eta(int lik, double yn, double isig2, const double (&eta)[T], double (&l)[T],
+                                                double (&mu)[T]) {
     if (lik == kGlmBernoulli) {
 #pragma unroll
-        for (int i = 0; i < kPredT; ++i) {
+        for (int i = 0; i < T; ++i) {
             const double ex = exp_lane(-fabs(eta[i]));
             mu[i] = ((eta[i] >= 0.0) ? 1.0 : ex) / (1.0 + ex);
             l[i] = yn * eta[i] - (fmax(eta[i], 0.0) + log1p_unit(ex));
         }
     } else if (lik == kGlmPoisson) {
 #pragma unroll
-        for (int i = 0; i < kPredT; ++i) {
+        for (int i = 0; i < T; ++i) {
             mu[i] = exp_lane(eta[i]);
             l[i] = yn * eta[i] - mu[i];
         }
     } else {
 #pragma unroll
-        for (int i = 0; i < kPredT; ++i) {
+        for (int i = 0; i < T; ++i) {
             const double res = yn - eta[i];
             mu[i] = eta[i];
             l[i] = -0.5 * ((res * res) * isig2);

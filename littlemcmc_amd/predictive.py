@@ -12,7 +12,8 @@ one backend, the HIP kernel; the merge / finalise logic above it is plain tensor
 restatement of the kernel's block through ``stats_fn`` (as ``diagnostics.summarize`` does).
 
 Further down: PSIS-LOO (``psis``, ``loo``; csrc/lmc_psis.hip) and posterior predictions at new X (``linear_predictor``,
-``predict``; csrc/lmc_linpred.hip), each with its own kernel and its own injected model in the CPU tests.
+``predict``; csrc/lmc_linpred.hip) and replicated responses (``replicate``, ``predict_response``, ``ppc``; csrc/lmc_yrep.hip),
+each with its own kernel and its own injected model in the CPU tests.
 
 What the passes over the trace share is stated once, in ``diagnostics``: ``_trace_job`` answers "what is x?" (one tensor or
 the per-GPU blocks of a job, chains per group, the groups touched) with every refusal, each pass naming the rule it wants in
@@ -559,3 +560,206 @@ def predict(x, target, X_new=None, probs=(0.05, 0.5, 0.95), chains_per_group=Non
     return dict(eta_mean=eta_mean, eta_sd=torch.sqrt(eta_var), mu_mean=mu_mean, mu_sd=torch.sqrt(mu_var),
                 eta_quantiles=torch.cat(eta_q, dim=-1)[..., :n_new], mu_quantiles=torch.cat(mu_q, dim=-1)[..., :n_new],
                 y_mean=y_mean, y_var=y_var, n=S, probs=probs)
+
+
+# ---- replicated responses (csrc/lmc_yrep.hpp, csrc/lmc_yrep.hip; include/lmc_hip.h: lmc_glm_yrep, lmc_glm_yrep_stats) --------
+PPC_NAMES = ("mean", "sd", "min", "max", "zeros", "chisq")
+
+
+def _seed32(random_seed):
+    return int(random_seed) & 0xFFFFFFFF
+
+
+def _hip_yrep(x, table, first_chain, per, ob0, ob1, seed):
+    """One call of lmc_glm_yrep: x[chains, draws, d] (a ROCm tensor), table[n_rows, row_len] on the same device ->
+    y[chains, draws, W], W = 64 (ob1 - ob0)."""
+    c, n, _d = x.shape
+    n_rows, row_len = table.shape
+    y = torch.empty((c, n, 64 * (int(ob1) - int(ob0))), dtype=torch.float64, device=x.device)
+    diagnostics._call_trace_kernel("lmc_glm_yrep", x, table, row_len, n_rows, int(first_chain), int(per), int(ob0), int(ob1),
+                                   int(seed), y)
+    return y
+
+
+def _yrep_block(b, target, table, cache, first, per, ob0, ob1, seed, yrep_fn):
+    if yrep_fn is not None:
+        return yrep_fn(b, table, first, per, ob0, ob1, seed)
+    b = diagnostics._device_block(b)
+    return _hip_yrep(b, _table_on(target, table, b.device, cache), first, per, ob0, ob1, seed)
+
+
+def replicate(x, target, X_new=None, obs_blocks=None, random_seed=0, yrep_fn=None):
+    """Replicated responses ``y_rep ~ p(y | q_s)`` of every draw, from ONE tensor of draws ``x[chains, draws, d]`` (the whole
+    job of ``target``) -> ``y[chains, draws, W]`` on the device: ``y[c, t, i]`` is a bernoulli / poisson / gaussian response at
+    ``X_new[64 * ob0 + i]`` under draw t of chain c -- a pure function of ``(random_seed, c, t, observation)``
+    (include/lmc_hip.h states the stream), whatever the chunking or the device; counts are doubles, observations beyond N_new
+    are padding (0), and a draw whose mean response is NaN, infinite or (poisson) above 2^52 gives NaN. It is N_new / d times
+    the trace: meant for tests and small jobs, :func:`predict_response` walks it in chunks and :func:`ppc` never writes it.
+    ``X_new``, ``obs_blocks`` as for :func:`linear_predictor`; ``yrep_fn(x, table, first_chain, per, ob0, ob1, seed) -> y``
+    replaces the HIP call."""
+    if isinstance(x, (list, tuple)):
+        raise ValueError("replicate takes one tensor; predict_response() and ppc() take the list of per-GPU blocks of a job")
+    members = _members(target)
+    job = diagnostics._trace_job(x, None, 0, target, whole_job=True)
+    table, n_new = _predicted(target, members, X_new)
+    nob = (n_new + 63) // 64
+    ob0, ob1 = (0, nob) if obs_blocks is None else (int(obs_blocks[0]), int(obs_blocks[1]))
+    if not (0 <= ob0 < ob1 <= nob):
+        raise ValueError("obs_blocks=%r of %d: a half-open, non-empty range" % (obs_blocks, nob))
+    return _yrep_block(job.held[0], target, table, None if X_new is None else {}, 0, job.per, ob0, ob1, _seed32(random_seed),
+                       yrep_fn)
+
+
+def _probs(probs):
+    probs = [float(p) for p in (probs.tolist() if hasattr(probs, "tolist") else probs)]
+    if not probs or any(not (0.0 <= p <= 1.0) for p in probs):
+        raise ValueError("probs must be a non-empty sequence of numbers in [0, 1] (got %r)" % (probs,))
+    return probs
+
+
+def predict_response(x, target, X_new=None, probs=(0.05, 0.5, 0.95), chains_per_group=None, scratch_bytes=1 << 30,
+                     random_seed=0, yrep_fn=None, count_fn=None):
+    """The prediction band of a NEW response of a ``GLM`` (leading axis 1) or of every posterior of a ``Batched`` of GLMs
+    (leading axis G) at the points ``X_new`` (as for :func:`predict`; ``None``: the training design), from the draws in HBM:
+    a dict with ``y_quantiles[G, P, N_new]``, the quantiles at ``probs`` of the S = chains of a group x draws replicated
+    responses of each point (one per draw: :func:`replicate`), ``y_min`` and ``y_max`` ``[G, N_new]``, ``n`` = S and ``probs``.
+
+    The order statistics are EXACT (the radix select on the written ``y_rep``) and the quantiles are interpolated between
+    them as numpy's default does -- also for counts: the 0.05 quantile of a poisson response may be 2.35. Take ``floor`` /
+    ``ceil`` of the two ends for an integer interval that covers at least the nominal mass. A point with a NaN replicate has
+    NaN quantiles, as numpy's are. The result is a pure function of ``random_seed`` and the draws: ``scratch_bytes`` (the
+    chunking over blocks of 64 observations, as in :func:`predict`), the list of per-GPU blocks and the devices do not change
+    a bit. ``yrep_fn`` (see :func:`replicate`) and ``count_fn`` (``diagnostics.order_statistics``) replace the two HIP calls."""
+    import math
+
+    from . import _abi
+
+    members = _members(target)
+    job = diagnostics._trace_job(x, chains_per_group, 0, target, whole_job=True)   # a group may straddle blocks
+    per, n_draws, dev = job.per, job.n_draws, job.device
+    probs = _probs(probs)
+    table, n_new = _predicted(target, members, X_new)
+    G, Q, S = len(members), len(probs), per * n_draws
+    chains = per * G
+    h = [p * (S - 1) for p in probs]
+    lo = [int(math.floor(v)) for v in h]
+    hi = [min(k + 1, S - 1) for k in lo]
+    ranks = [0, S - 1] + lo + hi
+    unit = chains * n_draws * 64 * 8
+    count_unit = 256 * 64 * 8 * min(len(set(ranks)), _abi.SELECT_MAX_RANKS)
+    nob = (n_new + 63) // 64
+    step = min(int(scratch_bytes) // (unit + count_unit), nob)
+    if step < 1:
+        raise ValueError("scratch_bytes=%d is below one block of 64 observations of the replicated responses, %d chains x %d "
+                         "draws x 64 x 8 = %d bytes, plus %d bytes of the select's counts of it" % (int(scratch_bytes), chains,
+                                                                                                    n_draws, unit, count_unit))
+    frac = torch.tensor([a - b for a, b in zip(h, lo)], dtype=torch.float64, device=dev).reshape(Q, 1)
+    cache = None if X_new is None else {}
+    seed = _seed32(random_seed)
+    y_q, y_min, y_max = [], [], []
+    for ob0 in range(0, nob, step):
+        ob1 = min(ob0 + step, nob)
+        W = 64 * (ob1 - ob0)
+        ys = [_yrep_block(b, target, table, cache, f, per, ob0, ob1, seed, yrep_fn) for b, f in zip(job.held, job.firsts)]
+        os_ = diagnostics.order_statistics(ys if len(ys) > 1 else ys[0], ranks, chains_per_group=per,
+                                           scratch_bytes=int(scratch_bytes) - (ob1 - ob0) * unit, count_fn=count_fn)
+        del ys
+        vmin, vmax = os_[:, 0], os_[:, 1]
+        vlo, vhi = os_[:, 2:2 + Q], os_[:, 2 + Q:]
+        bad = (torch.isnan(vmin) | torch.isnan(vmax)).unsqueeze(1)
+        nan = torch.full((G, Q, W), float("nan"), dtype=torch.float64, device=dev)
+        y_q.append(torch.where(bad, nan, vlo + (vhi - vlo) * frac))
+        y_min.append(vmin)
+        y_max.append(vmax)
+    return dict(y_quantiles=torch.cat(y_q, dim=-1)[..., :n_new], y_min=torch.cat(y_min, dim=-1)[..., :n_new],
+                y_max=torch.cat(y_max, dim=-1)[..., :n_new], n=S, probs=probs)
+
+
+def _hip_yrep_stats(x, table, first_chain, per, seed, centre):
+    """One call of lmc_glm_yrep_stats: x[chains, draws, d] (a ROCm tensor), table[n_rows, row_len] and centre[n_rows] on the
+    same device -> T[chains, draws, 7]."""
+    from . import _abi
+
+    c, n, _d = x.shape
+    n_rows, row_len = table.shape
+    T = torch.empty((c, n, _abi.YREP_STATS), dtype=torch.float64, device=x.device)
+    diagnostics._call_trace_kernel("lmc_glm_yrep_stats", x, table, row_len, n_rows, int(first_chain), int(per), int(seed), centre, T)
+    return T
+
+
+def ppc_scales(T, n_obs, centre):
+    """The five statistics of a data set on their own scales from the planes ``T[..., 0:5]`` (sum, sum of squares about
+    ``centre``, min, max, zeros) of its N = ``n_obs`` values: ``[..., 5]`` = mean ``P0 / N``, sd ``sqrt(var)`` with
+    ``var = (P1 - (P0 - N c)^2 / N) / (N - 1)`` (clamped at 0; NaN for N = 1), min, max, zeros. ``centre`` broadcasts
+    against ``T[..., 0]``. The observed data go through the same expression, so ties compare equal."""
+    N = float(n_obs)
+    P0, P1 = T[..., 0], T[..., 1]
+    dev = P0 - N * centre
+    var = (P1 - dev * dev / N) / (N - 1.0) if n_obs > 1 else torch.full_like(P0, float("nan"))
+    sd = torch.sqrt(torch.where(var < 0.0, torch.zeros_like(var), var))
+    return torch.stack([P0 / N, sd, T[..., 2], T[..., 3], T[..., 4]], dim=-1)
+
+
+def _sum_by_group(v, first, per):
+    """v[c, k] of a block whose chain 0 is job chain ``first`` -> [groups touched, k]: the rows of every group's chains added."""
+    c = int(v.shape[0])
+    g0, touched = diagnostics._touched(first, c, per)
+    if first % per == 0 and c % per == 0:
+        return v.reshape(touched, per, -1).sum(dim=1)
+    cuts = [min(max((g0 + i) * per - first, 0), c) for i in range(touched + 1)]
+    return torch.stack([v[a:b].sum(dim=0) for a, b in zip(cuts[:-1], cuts[1:])])
+
+
+def ppc(x, target, random_seed=0, probs=(0.05, 0.5, 0.95), chains_per_group=None, stats_fn=None, count_fn=None, **kw):
+    """Posterior predictive checks of a ``GLM`` (leading axis 1) or of every posterior of a ``Batched`` of GLMs (leading axis
+    G) from the draws in HBM: does the fitted model reproduce the data? Every draw s gives one replicated data set
+    ``y_rep ~ p(y | q_s)`` at the training design (the values of :func:`replicate` on the same ``random_seed``, never
+    written), reduced on the device to test statistics (``lmc_glm_yrep_stats``); a dict of float64 tensors on x's device:
+
+    ``T_obs[G, 5]``: mean, sd, min, max and number of zeros of the observed ``y`` (``names[:5]``);
+    ``T_rep_mean[G, 5]``, ``T_rep_quantiles[G, P, 5]``: the mean over the S draws, and the quantiles at ``probs``
+    (``diagnostics.quantiles``: exact order statistics, numpy's interpolation), of the same five statistics of the
+    replicated data sets, each on its own scale (:func:`ppc_scales`);
+    ``p_value[G, 6]``: the posterior predictive p-value (Gelman, Meng, Stern 1996) -- the share of draws with
+    ``T(y_rep) >= T(y)`` for the five statistics, and with ``X^2(y_rep, q_s) >= X^2(y, q_s)`` for ``chisq``, Pearson's
+    ``sum_i (y_i - mu_i)^2 / V_i``, whose realised value depends on the draw. A value near 0 or 1 says the data are extreme
+    under the model: ``chisq`` near 0 is overdispersion, ``zeros`` near 0 excess zeros. A draw with a NaN statistic counts as
+    "not >=";
+    ``names`` = ``PPC_NAMES``, ``n`` = S, ``probs``.
+
+    ``x`` is one tensor ``[chains, draws, d]`` or the list of per-GPU blocks of the job; the counts of the p-values are integers
+    added over blocks and the select is exact, so a posterior may straddle devices (``T_rep_mean`` is then a sum of parts).
+    The kernel's planes ``T[chains, draws, 7]`` of a block live on its device until its counts are taken; only the five scaled
+    statistics (``5 / N`` of what ``y_rep`` would be) are kept for the select.
+    ``**kw`` goes to the select (``scratch_bytes``). ``stats_fn(x, table, first_chain, per, seed, centre) -> T[chains, draws,
+    7]`` and ``count_fn`` replace the two HIP calls (tests of this logic)."""
+    members = _members(target)
+    job = diagnostics._trace_job(x, chains_per_group, 0, target, whole_job=True)   # a group may straddle blocks
+    per, dev, S = job.per, job.device, job.per * job.n_draws
+    probs = _probs(probs)
+    G, n_obs = len(members), members[0].n_obs
+    table = np.ascontiguousarray(target.params, dtype=np.float64).reshape(G, -1)
+    seed = _seed32(random_seed)
+    centre = np.array([float(m.y.sum()) / n_obs for m in members], dtype=np.float64)
+    planes_obs = np.array([[m.y.sum(), ((m.y - c) ** 2).sum(), m.y.min(), m.y.max(), float((m.y == 0.0).sum())]
+                           for m, c in zip(members, centre)], dtype=np.float64)
+    T_obs = ppc_scales(torch.from_numpy(planes_obs), n_obs, torch.from_numpy(centre)).to(dev)
+    scaled = []
+
+    def call(b, first):   # the five scales stay on the block's device; what is merged are sums and counts per group
+        if stats_fn is not None:
+            T = stats_fn(b, table, first, per, seed, centre)
+        else:
+            b = diagnostics._device_block(b)
+            T = _hip_yrep_stats(b, _table_on(target, table, b.device), first, per, seed, torch.from_numpy(centre).to(b.device))
+        g = (first + torch.arange(int(b.shape[0]), device=T.device)) // per
+        tr = ppc_scales(T, n_obs, torch.from_numpy(centre).to(T.device)[g].unsqueeze(1))
+        scaled.append(tr)
+        ge = torch.cat([tr >= T_obs.to(T.device)[g].unsqueeze(1), (T[..., 5] >= T[..., 6]).unsqueeze(-1)], dim=-1)
+        per_chain = torch.cat([tr.sum(dim=1), ge.sum(dim=1).to(torch.float64)], dim=-1)   # [c, 5 + 6]; counts are exact
+        return _sum_by_group(per_chain, first, per)
+
+    tot = diagnostics._fan_out(job, 0, G, call, torch.add)
+    q = diagnostics.quantiles(scaled if len(scaled) > 1 else scaled[0], probs, chains_per_group=per, count_fn=count_fn, **kw)
+    return dict(T_obs=T_obs, T_rep_mean=tot[:, :5] / float(S), T_rep_quantiles=q["quantiles"], p_value=tot[:, 5:] / float(S),
+                names=PPC_NAMES, n=S, probs=probs)

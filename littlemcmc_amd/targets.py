@@ -250,6 +250,27 @@ class GLM(DeviceTarget):
 
         return predictive.predict(x, self, X_new, **kw)
 
+    def replicate(self, x, X_new=None, **kw):
+        """``predictive.replicate(x, self, X_new, ...)``: the replicated responses ``y_rep[chains, draws, W]`` of every draw in
+        HBM at ``X_new`` (default: the training design), a pure function of ``random_seed``."""
+        from . import predictive
+
+        return predictive.replicate(x, self, X_new, **kw)
+
+    def predict_response(self, x, X_new=None, **kw):
+        """``predictive.predict_response(x, self, X_new, ...)``: the prediction band of a NEW response at ``X_new`` -- exact
+        quantiles ``y_quantiles[1, P, N_new]``, ``y_min``, ``y_max`` of the replicated responses of the draws in HBM."""
+        from . import predictive
+
+        return predictive.predict_response(x, self, X_new, **kw)
+
+    def ppc(self, x, **kw):
+        """``predictive.ppc(x, self, ...)``: posterior predictive checks of the draws ``x`` in HBM (leading axis 1) -- mean, sd,
+        min, max, zeros and Pearson chi-square of replicated data sets against the observed ``y``, with their p-values."""
+        from . import predictive
+
+        return predictive.ppc(x, self, **kw)
+
     def covariance(self, x, **kw):
         """``diagnostics.covariance(x, ...)``: posterior covariance, correlation and sd of the coefficients from the draws ``x`` in
         HBM -- ``cov[d, d]``, ``corr[d, d]``, ``sd[d]``, ``mean[d]``."""
@@ -797,6 +818,27 @@ class Batched(DeviceTarget):
         from . import predictive
 
         return predictive.predict(x, self, X_new, **kw)
+
+    def replicate(self, x, X_new=None, **kw):
+        """``predictive.replicate(x, self, X_new, ...)`` (GLM members): the replicated responses ``y_rep[chains, draws, W]`` of
+        every draw at ``X_new`` (a list of G designs; default: each member's training design)."""
+        from . import predictive
+
+        return predictive.replicate(x, self, X_new, **kw)
+
+    def predict_response(self, x, X_new=None, **kw):
+        """``predictive.predict_response(x, self, X_new, ...)`` per posterior (GLM members): the prediction band of a new
+        response, ``y_quantiles[G, P, N_new]``, ``y_min``, ``y_max``, from the draws in HBM."""
+        from . import predictive
+
+        return predictive.predict_response(x, self, X_new, **kw)
+
+    def ppc(self, x, **kw):
+        """``predictive.ppc(x, self, ...)`` per posterior (GLM members): posterior predictive checks ``T_obs[G, 5]``,
+        ``T_rep_mean``, ``T_rep_quantiles``, ``p_value[G, 6]`` of all groups in one pass over the draws in HBM."""
+        from . import predictive
+
+        return predictive.ppc(x, self, **kw)
 
     def __repr__(self):
         return "Batched(%d x %s, d=%d)" % (self.groups, type(self.members[0]).__name__, self.d)
