@@ -47,12 +47,8 @@ __device__ __forceinline__ void lin_merge(double na, LinStats& a, double nb, con
     }
     const double n = na + nb;
     const double w = nb / n, cross = na * nb / n;
-    const double de = b.mean_e - a.mean_e;
-    a.mean_e = a.mean_e + de * w;
-    a.M2_e = (a.M2_e + b.M2_e) + (de * de) * cross;
-    const double dm = b.mean_m - a.mean_m;
-    a.mean_m = a.mean_m + dm * w;
-    a.M2_m = (a.M2_m + b.M2_m) + (dm * dm) * cross;
+    chan_merge(w, cross, a.mean_e, a.M2_e, b.mean_e, b.M2_e);
+    chan_merge(w, cross, a.mean_m, a.M2_m, b.mean_m, b.M2_m);
 }
 
 // eta_out[chain][t][W] and / or partial[chain][segment][obs block][5][64] (either may be NULL, not both)
@@ -64,11 +60,7 @@ __global__ __launch_bounds__(64) void linpred_kernel(const double* __restrict__ 
     const int obr = static_cast<int>(blockIdx.x % static_cast<unsigned>(nobr));
     const long long cs = blockIdx.x / static_cast<unsigned>(nobr);   // (chain, segment): the order of the partials
     const long long c = cs / segs, seg = cs % segs;
-    // the chain's row: wave-uniform (the header is read on the scalar unit); its y section is skipped, never read
-    const double* row = rows + ((first_chain + c) / per) * row_len;
-    const int lik = first_i32(static_cast<int>(row[0]));
-    const GRow xt = reinterpret_cast<GRow>(reinterpret_cast<unsigned long long>(row + kGlmHeader)) + npad;
-    const unsigned row_bytes = static_cast<unsigned>(npad) * 8u;
+    const GlmRowView row = glm_row_view(rows, row_len, npad, (first_chain + c) / per);   // its y section is never read
     const unsigned col0 = (static_cast<unsigned>(ob0 + obr) * 64u + lane) * 8u;   // padding observations: X = 0 -> eta = 0
     const double* xc = x + (c * draws_stride + t0) * dim;
     const long long W = static_cast<long long>(nobr) * 64;
@@ -76,12 +68,11 @@ __global__ __launch_bounds__(64) void linpred_kernel(const double* __restrict__ 
 
     LinStats acc = {0.0, 0.0, 0.0, 0.0};
     double cnt = 0.0;
-    const long long ta = seg * kLinSeg;
-    const long long tb = (n - ta < kLinSeg) ? n : ta + kLinSeg;
-    for (long long t = ta; t < tb; t += kPredT) {
-        const int k = (tb - t < kPredT) ? static_cast<int>(tb - t) : kPredT;   // draws of this tile (wave-uniform)
+    const DrawWindow win = draw_window(seg, kLinSeg, n);
+    for (long long t = win.ta; t < win.tb; t += kPredT) {
+        const int k = (win.tb - t < kPredT) ? static_cast<int>(win.tb - t) : kPredT;   // draws of this tile (wave-uniform)
         double eta[kPredT];
-        glm_eta_tile(xc + t * dim, k, dim, xt, col0, row_bytes, eta);
+        glm_eta_tile(xc + t * dim, k, dim, row.xt, col0, row.row_bytes, eta);
         if (o) {
 #pragma unroll
             for (int i = 0; i < kPredT; ++i)
@@ -89,10 +80,7 @@ __global__ __launch_bounds__(64) void linpred_kernel(const double* __restrict__ 
         }
         if (partial) {   // (wave-uniform)
             double l[kPredT], mu[kPredT];
-            glm_link_of_eta(lik, 0.0, 0.0, eta, l, mu);   // mu alone: l is dropped
-#pragma unroll
-            for (int i = 0; i < kPredT; ++i)              // a NaN eta is a NaN mu: exp_lane clamps its argument through
-                mu[i] = (eta[i] != eta[i]) ? eta[i] : mu[i];   // fmax / fmin, which would swallow it (mu = 0)
+            glm_mu_of_eta(row.lik, eta, l, mu);
             // ---- the tile's statistics: two passes; a tile's missing draws repeat its last one and are deselected
             double se = 0.0, sm = 0.0;
 #pragma unroll

@@ -1,11 +1,7 @@
 // Sixth translation unit of liblmc_hip.so: Pareto-smoothed importance sampling leave-one-out (PSIS-LOO; Vehtari, Gelman,
-// Gabry 2017) on the draws where they live (HBM). include/lmc_hip.h states the row algorithm (lmc_psis_rows) and the layout
-// of the pointwise log-likelihood array (lmc_glm_pointwise_loglik); littlemcmc_amd/predictive.py: psis(), loo().
-//
-// pointwise_loglik_kernel: one wavefront per (group, chain of the group, observation block), lane = observation; it walks
-// the chain's draws kPredT at a time through glm_link_tile (lmc_predict_tile.hpp) -- the function pointwise_kernel reduces,
-// so the l written here are the bits reduced there -- and every lane stores its tile's l as up to kPredT consecutive
-// doubles of its row out[group][observation][chain * n + t].
+// Gabry 2017) of rows of log-likelihood values in HBM. include/lmc_hip.h states the row algorithm (lmc_psis_rows);
+// littlemcmc_amd/predictive.py: psis(), loo(). It knows nothing of GLMs: the rows that loo() hands it are written by
+// pointwise_loglik_kernel (lmc_predict.hip), and any other log-likelihood array will do.
 //
 // psis_rows_kernel: one workgroup of kPsisThreads per row, ten passes over the row (256 KB at S = 32 000: it stays in L2):
 //   pass 1      min l (c = -min l) and whether every l is finite
@@ -20,15 +16,10 @@
 // Every floating-point sum is taken in a fixed order -- a thread's elements ascending, the wavefront by a xor butterfly, the
 // wavefronts ascending -- so two calls on the same data give the same bits. LDS: the tail (32 KiB), the histogram (2 KiB),
 // the fit's partial sums and candidates (5 KiB) and a few scalars, 40 KiB in all.
-// lmc_glm_pointwise_loglik's checks of the trace view, the grouping and the GLM table are trace_span, glm_span and
-// glm_check_headers (lmc_trace_pass.hpp), shared by every pass over the trace; lmc_psis_rows is no such pass.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/lmc_hip.h"
-#include "lmc_predict_tile.hpp"
-#include "lmc_targets.hpp"
-#include "lmc_trace_pass.hpp"
 
 namespace lmc {
 
@@ -39,35 +30,6 @@ constexpr int kPsisOwn = kPsisMaxTail / kPsisThreads;   // tail elements a threa
 constexpr int kPsisMaxCand = 30 + 64;                     // m = 30 + floor(sqrt(n_tail)), n_tail <= 4096
 constexpr double kLogDblMin = -708.39641853226410622;     // log(DBL_MIN), rounded to nearest
 static_assert(kPsisMaxTail == 4096 && kPsisOwn * kPsisThreads == kPsisMaxTail && kPsisWaves == 4, "the tail plan");
-
-__global__ __launch_bounds__(64) void pointwise_loglik_kernel(const double* __restrict__ x, long long draws_stride, int dim,
-                                                              long long t0, long long n, const double* __restrict__ rows,
-                                                              long long row_len, int npad, int ob0, int nobr, long long per,
-                                                              long long g0, double* __restrict__ out) {
-    const unsigned lane = threadIdx.x;
-    const int ob = ob0 + static_cast<int>(blockIdx.x % static_cast<unsigned>(nobr));
-    const long long gc = blockIdx.x / static_cast<unsigned>(nobr);   // chain of the block (whole groups: gi * per + cg)
-    const long long gi = gc / per, cg = gc % per;
-    const double* row = rows + (g0 + gi) * row_len;
-    const int lik = first_i32(static_cast<int>(row[0]));
-    const double isig2 = row[4];
-    const GRow y = reinterpret_cast<GRow>(reinterpret_cast<unsigned long long>(row + kGlmHeader));
-    const GRow xt = y + npad;
-    const unsigned row_bytes = static_cast<unsigned>(npad) * 8u;
-    const unsigned col0 = (static_cast<unsigned>(ob) * 64u + lane) * 8u;
-    const double yn = grow_at(y, col0);
-    const double* xc = x + (gc * draws_stride + t0) * dim;
-    const long long S = per * n;
-    double* o = out + ((gi * nobr + (ob - ob0)) * 64 + lane) * S + cg * n;
-    for (long long t = 0; t < n; t += kPredT) {
-        const int k = (n - t < kPredT) ? static_cast<int>(n - t) : kPredT;
-        double l[kPredT], mu[kPredT];
-        glm_link_tile(xc + t * dim, k, dim, xt, col0, row_bytes, lik, yn, isig2, l, mu);
-#pragma unroll
-        for (int i = 0; i < kPredT; ++i)
-            if (i < k) o[t + i] = l[i];
-    }
-}
 
 // order-preserving key of a double: a < b  <=>  key(a) < key(b) (-0 below +0; no NaN reaches it)
 __device__ __forceinline__ unsigned long long psis_key(double v) {
@@ -295,33 +257,7 @@ __global__ __launch_bounds__(kPsisThreads) void psis_rows_kernel(const double* _
 
 }  // namespace lmc
 
-// See include/lmc_hip.h. x, rows and out are DEVICE pointers on the current device; the work is enqueued on `stream`.
-extern "C" int lmc_glm_pointwise_loglik(const double* x, int64_t chains, int64_t draws_stride, int32_t dim, int64_t t0, int64_t n,
-                                        const double* rows, int64_t row_len, int64_t n_rows, int64_t first_chain,
-                                        int64_t chains_per_group, int64_t ob0, int64_t ob1, double* out, void* stream) {
-    using namespace lmc;
-    const int64_t lim = int64_t(1) << 31;
-    TraceSpan span;
-    GlmSpan glm;
-    if (!out || trace_span(x, chains, draws_stride, dim, t0, n, first_chain, chains_per_group, &span) != LMC_OK) return LMC_ERR_INVALID;
-    // whole groups: then chains_per_group <= chains < 2^31 (span.per is it), g0 = first_chain / per and groups = chains / per
-    if (first_chain % chains_per_group != 0 || chains % chains_per_group != 0) return LMC_ERR_INVALID;
-    if (glm_span(rows, row_len, n_rows, dim, span, ob0, ob1, &glm) != LMC_OK) return LMC_ERR_INVALID;
-    const int64_t per = span.per, g0 = span.g0, npad = glm.npad;
-    const int64_t nobr = ob1 - ob0;
-    const int64_t blocks = chains * nobr;
-    if (blocks >= lim) return LMC_ERR_INVALID;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int hdr_rc = glm_check_headers(rows, row_len, span, npad, dim, s);
-    if (hdr_rc != LMC_OK) return hdr_rc;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(pointwise_loglik_kernel, dim3(static_cast<unsigned>(blocks)), dim3(64), 0, s, x,
-                       static_cast<long long>(draws_stride), dim, static_cast<long long>(t0), static_cast<long long>(n), rows,
-                       static_cast<long long>(row_len), static_cast<int>(npad), static_cast<int>(ob0), static_cast<int>(nobr),
-                       static_cast<long long>(per), static_cast<long long>(g0), out);
-    return hipGetLastError() == hipSuccess ? LMC_OK : LMC_ERR_HIP;
-}
-
+// See include/lmc_hip.h. l and out are DEVICE pointers on the current device; the work is enqueued on `stream`.
 extern "C" int lmc_psis_rows(const double* l, int64_t rows, int64_t S, int64_t row_stride, int32_t tail_len, double* out,
                              void* stream) {
     using namespace lmc;

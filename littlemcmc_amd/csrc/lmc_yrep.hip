@@ -42,8 +42,7 @@ static_assert(kYrepOutSeg % kPredT == 0 && kYrepSeg % kYrepT == 0 && kYrepT <= k
 static_assert(kYrepPlanes == 7, "sum, sum of squares, min, max, zeros, two Pearson statistics");
 
 // y[i] = y_rep of the tile's draw i < k (wave-uniform k <= T) at the lane's observation `obs`; real = false (a padding
-// observation) gives 0 and draws nothing. y[i] for i >= k is 0. The mu of a NaN eta is made NaN first (exp_lane clamps its
-// argument through fmax / fmin, which would swallow it).
+// observation) gives 0 and draws nothing. y[i] for i >= k is 0. yrep_value asks eta itself for a NaN, so mu may be the link's.
 template <int T>
 __device__ __forceinline__ void yrep_tile(int lik, const double (&eta)[T], const double (&mu)[T], int k, double sigma,
                                           uint32_t seed, uint32_t chain, uint32_t r0, uint32_t obs, bool real, double (&y)[T]) {
@@ -73,29 +72,22 @@ __global__ __launch_bounds__(64) void yrep_kernel(const double* __restrict__ x, 
     const int obr = static_cast<int>(blockIdx.x % static_cast<unsigned>(nobr));
     const long long cs = blockIdx.x / static_cast<unsigned>(nobr);
     const long long c = cs / segs, seg = cs % segs;
-    // the chain's row: wave-uniform (the header is read on the scalar unit); its y section is skipped, never read
-    const double* row = rows + ((first_chain + c) / per) * row_len;
-    const int lik = first_i32(static_cast<int>(row[0]));
-    const int nobs = first_i32(static_cast<int>(row[1]));
-    const double sigma = 1.0 / sqrt(row[4]);
-    const GRow xt = reinterpret_cast<GRow>(reinterpret_cast<unsigned long long>(row + kGlmHeader)) + npad;
-    const unsigned row_bytes = static_cast<unsigned>(npad) * 8u;
+    const GlmRowView row = glm_row_view(rows, row_len, npad, (first_chain + c) / per);   // its y section is never read
     const unsigned obs = static_cast<unsigned>(ob0 + obr) * 64u + lane;
     const unsigned col0 = obs * 8u;
-    const bool real = obs < static_cast<unsigned>(nobs);
+    const bool real = obs < static_cast<unsigned>(row.nobs);
     const uint32_t chain = static_cast<uint32_t>(first_chain + c);
     const double* xc = x + (c * draws_stride + t0) * dim;
     const long long W = static_cast<long long>(nobr) * 64;
     double* o = y_out + c * n * W + obr * 64 + lane;
 
-    const long long ta = seg * kYrepOutSeg;
-    const long long tb = (n - ta < kYrepOutSeg) ? n : ta + kYrepOutSeg;
-    for (long long t = ta; t < tb; t += kPredT) {
-        const int k = (tb - t < kPredT) ? static_cast<int>(tb - t) : kPredT;   // draws of this tile (wave-uniform)
+    const DrawWindow win = draw_window(seg, kYrepOutSeg, n);
+    for (long long t = win.ta; t < win.tb; t += kPredT) {
+        const int k = (win.tb - t < kPredT) ? static_cast<int>(win.tb - t) : kPredT;   // draws of this tile (wave-uniform)
         double eta[kPredT], l[kPredT], mu[kPredT], y[kPredT];
-        glm_eta_tile(xc + t * dim, k, dim, xt, col0, row_bytes, eta);
-        glm_link_of_eta(lik, 0.0, 0.0, eta, l, mu);   // mu alone: l is dropped
-        yrep_tile<kPredT>(lik, eta, mu, k, sigma, seed, chain, static_cast<uint32_t>(t0 + t), obs, real, y);
+        glm_eta_tile(xc + t * dim, k, dim, row.xt, col0, row.row_bytes, eta);
+        glm_link_of_eta(row.lik, 0.0, 0.0, eta, l, mu);   // mu alone: l is dropped, and yrep_value asks eta for a NaN itself
+        yrep_tile<kPredT>(row.lik, eta, mu, k, row.sigma, seed, chain, static_cast<uint32_t>(t0 + t), obs, real, y);
 #pragma unroll
         for (int i = 0; i < kPredT; ++i)
             if (i < k) o[(t + i) * W] = y[i];   // 64 lanes, 64 consecutive doubles: one 512-byte row
@@ -138,23 +130,15 @@ __global__ __launch_bounds__(64) void yrep_stats_kernel(const double* __restrict
     const unsigned lane = threadIdx.x;
     const long long c = blockIdx.x / segs, seg = blockIdx.x % segs;
     const long long g = (first_chain + c) / per;
-    const double* row = rows + g * row_len;   // wave-uniform
-    const int lik = first_i32(static_cast<int>(row[0]));
-    const int nobs = first_i32(static_cast<int>(row[1]));
-    const double isig2 = row[4];
-    const double sigma = 1.0 / sqrt(isig2);
+    const GlmRowView row = glm_row_view(rows, row_len, npad, g);   // wave-uniform
     const double cen = centre[g];
-    const GRow ysec = reinterpret_cast<GRow>(reinterpret_cast<unsigned long long>(row + kGlmHeader));
-    const GRow xt = ysec + npad;
-    const unsigned row_bytes = static_cast<unsigned>(npad) * 8u;
     const uint32_t chain = static_cast<uint32_t>(first_chain + c);
     const double* xc = x + (c * draws_stride + t0) * dim;
     double* out = T + c * n * kYrepPlanes;
 
-    const long long ta = seg * kYrepSeg;
-    const long long tb = (n - ta < kYrepSeg) ? n : ta + kYrepSeg;
-    for (long long t = ta; t < tb; t += kYrepT) {
-        const int k = (tb - t < kYrepT) ? static_cast<int>(tb - t) : kYrepT;   // draws of this tile (wave-uniform)
+    const DrawWindow win = draw_window(seg, kYrepSeg, n);
+    for (long long t = win.ta; t < win.tb; t += kYrepT) {
+        const int k = (win.tb - t < kYrepT) ? static_cast<int>(win.tb - t) : kYrepT;   // draws of this tile (wave-uniform)
         double a_sum[kYrepT], a_sq[kYrepT], a_min[kYrepT], a_max[kYrepT], a_zero[kYrepT], a_rep[kYrepT], a_obs[kYrepT];
 #pragma unroll
         for (int i = 0; i < kYrepT; ++i) {
@@ -165,17 +149,15 @@ __global__ __launch_bounds__(64) void yrep_stats_kernel(const double* __restrict
         for (int ob = 0; ob < nob; ++ob) {
             const unsigned obs = static_cast<unsigned>(ob) * 64u + lane;
             const unsigned col0 = obs * 8u;
-            const bool real = obs < static_cast<unsigned>(nobs);
-            const double yn = grow_at(ysec, col0);
+            const bool real = obs < static_cast<unsigned>(row.nobs);
+            const double yn = grow_at(row.y, col0);
             double eta[kYrepT], l[kYrepT], mu[kYrepT], y[kYrepT];
-            glm_eta_tile(xc + t * dim, k, dim, xt, col0, row_bytes, eta);   // (a tile of kYrepT draws: the width is the array's)
-            glm_link_of_eta(lik, 0.0, 0.0, eta, l, mu);
-#pragma unroll
-            for (int i = 0; i < kYrepT; ++i) mu[i] = (eta[i] != eta[i]) ? eta[i] : mu[i];
-            yrep_tile<kYrepT>(lik, eta, mu, k, sigma, seed, chain, static_cast<uint32_t>(t0 + t), obs, real, y);
+            glm_eta_tile(xc + t * dim, k, dim, row.xt, col0, row.row_bytes, eta);   // (a tile of kYrepT draws: the width is the array's)
+            glm_mu_of_eta(row.lik, eta, l, mu);   // the Pearson sums below want a NaN draw's mu NaN
+            yrep_tile<kYrepT>(row.lik, eta, mu, k, row.sigma, seed, chain, static_cast<uint32_t>(t0 + t), obs, real, y);
 #pragma unroll
             for (int i = 0; i < kYrepT; ++i) {
-                const double V = (lik == kGlmBernoulli) ? mu[i] * (1.0 - mu[i]) : (lik == kGlmPoisson) ? mu[i] : 1.0 / isig2;
+                const double V = (row.lik == kGlmBernoulli) ? mu[i] * (1.0 - mu[i]) : (row.lik == kGlmPoisson) ? mu[i] : 1.0 / row.isig2;
                 const double dc = y[i] - cen, dr = y[i] - mu[i], dy = yn - mu[i];
                 a_sum[i] += real ? y[i] : 0.0;
                 a_sq[i] += real ? dc * dc : 0.0;

@@ -687,6 +687,46 @@ def order_statistics(x, ranks, chains_per_group=None, scratch_bytes=1 << 30, cou
     return out if chains_per_group is not None else out[0]
 
 
+def _probs(probs):
+    """``probs`` as a list of floats, validated: the one refusal of every ``probs=`` of this package."""
+    probs = [float(p) for p in (probs.tolist() if hasattr(probs, "tolist") else probs)]
+    if not probs or any(not (0.0 <= p <= 1.0) for p in probs):
+        raise ValueError("probs must be a non-empty sequence of numbers in [0, 1] (got %r)" % (probs,))
+    return probs
+
+
+def _quantile_plan(S, probs):
+    """What the quantiles at ``probs`` of S sorted values v need, by numpy's default interpolation
+
+        h = p (S - 1),  lo = floor(h),  q = v[lo] + (v[min(lo + 1, S - 1)] - v[lo]) (h - lo)
+
+    -> (the validated probs, ranks = [0, S - 1] + lo + hi to hand to :func:`order_statistics`, frac = h - lo)."""
+    probs = _probs(probs)
+    h = [p * (S - 1) for p in probs]
+    lo = [int(math.floor(v)) for v in h]
+    hi = [min(k + 1, S - 1) for k in lo]
+    return probs, [0, S - 1] + lo + hi, [a - b for a, b in zip(h, lo)]
+
+
+def _interpolate(os_, frac, link=None):
+    """The select's result ``os_[..., 2 + 2 Q, d]`` at the ranks of :func:`_quantile_plan` -> (min[..., d], max[..., d],
+    quantiles[..., Q, d] = vlo + (vhi - vlo) frac). A column whose min or max is NaN holds a NaN value and all its quantiles
+    are NaN, as numpy's are. With ``link``, a monotone map, a fourth entry: the quantiles of link(v) -- the sorted link(v) ARE
+    the link of the sorted v, so the map is applied to vlo and vhi and the interpolation is done on its scale, no second select."""
+    Q = len(frac)
+    vmin, vmax = os_[..., 0, :], os_[..., 1, :]
+    vlo, vhi = os_[..., 2:2 + Q, :], os_[..., 2 + Q:, :]
+    frac = torch.tensor(frac, dtype=torch.float64, device=os_.device).reshape(Q, 1)
+    bad = (torch.isnan(vmin) | torch.isnan(vmax)).unsqueeze(-2)
+
+    def band(lo, hi):
+        q = lo + (hi - lo) * frac
+        return torch.where(bad, torch.full_like(q, float("nan")), q)
+
+    out = (vmin, vmax, band(vlo, vhi))
+    return out if link is None else out + (band(link(vlo), link(vhi)),)
+
+
 def quantiles(x, probs, chains_per_group=None, **kw):
     """Posterior quantiles from the trace in place -> dict(quantiles[Q, d], min[d], max[d], n, probs); with
     ``chains_per_group=per`` quantiles[G, Q, d], min[G, d], max[G, d]. With v the sorted S = chains x draws values of a
@@ -697,22 +737,10 @@ def quantiles(x, probs, chains_per_group=None, **kw):
     v[lo] and v[lo + 1] are exact (``order_statistics``; ``**kw`` goes there); ``min`` and ``max`` are ranks 0 and S - 1,
     always selected; ``n`` is S. A (group, dimension) whose min or max is NaN holds a NaN draw and all its quantiles are
     NaN, as numpy's are. ``probs`` must lie in [0, 1] and must not be empty."""
-    probs = [float(p) for p in (probs.tolist() if hasattr(probs, "tolist") else probs)]
-    if not probs or any(not (0.0 <= p <= 1.0) for p in probs):
-        raise ValueError("probs must be a non-empty sequence of numbers in [0, 1] (got %r)" % (probs,))
     job = _select_job(x, chains_per_group)
     S = job.per * job.n_draws
-    h = [p * (S - 1) for p in probs]
-    lo = [int(math.floor(v)) for v in h]
-    hi = [min(k + 1, S - 1) for k in lo]
-    os_ = order_statistics(x, [0, S - 1] + lo + hi, chains_per_group=chains_per_group, **kw)
-    Q = len(probs)
-    vmin, vmax = os_[..., 0, :], os_[..., 1, :]
-    vlo, vhi = os_[..., 2:2 + Q, :], os_[..., 2 + Q:, :]
-    frac = torch.tensor([a - b for a, b in zip(h, lo)], dtype=torch.float64, device=os_.device).reshape(Q, 1)
-    q = vlo + (vhi - vlo) * frac
-    bad = (torch.isnan(vmin) | torch.isnan(vmax)).unsqueeze(-2)
-    q = torch.where(bad, torch.full_like(q, float("nan")), q)
+    probs, ranks, frac = _quantile_plan(S, probs)
+    vmin, vmax, q = _interpolate(order_statistics(x, ranks, chains_per_group=chains_per_group, **kw), frac)
     return {"quantiles": q, "min": vmin, "max": vmax, "n": S, "probs": probs}
 
 

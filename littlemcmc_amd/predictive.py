@@ -11,15 +11,18 @@ constants that do not depend on the coefficients dropped); :func:`finalize` adds
 one backend, the HIP kernel; the merge / finalise logic above it is plain tensor code, and its CPU tests inject a numpy
 restatement of the kernel's block through ``stats_fn`` (as ``diagnostics.summarize`` does).
 
-Further down: PSIS-LOO (``psis``, ``loo``; csrc/lmc_psis.hip) and posterior predictions at new X (``linear_predictor``,
-``predict``; csrc/lmc_linpred.hip) and replicated responses (``replicate``, ``predict_response``, ``ppc``; csrc/lmc_yrep.hip),
+Further down: PSIS-LOO (``psis``, ``loo``; csrc/lmc_psis.hip smooths the array that ``lmc_glm_pointwise_loglik`` of
+csrc/lmc_predict.hip writes) and posterior predictions at new X (``linear_predictor``, ``predict``; csrc/lmc_linpred.hip) and
+replicated responses (``replicate``, ``predict_response``, ``ppc``; csrc/lmc_yrep.hip),
 each with its own kernel and its own injected model in the CPU tests.
 
 What the passes over the trace share is stated once, in ``diagnostics``: ``_trace_job`` answers "what is x?" (one tensor or
 the per-GPU blocks of a job, chains per group, the groups touched) with every refusal, each pass naming the rule it wants in
 one line; ``_fan_out`` runs a kernel on every block's device and folds the parts with :func:`merge` / :func:`merge_moments`;
-``_call_trace_kernel`` is the ctypes call. Here remain the kernels' outputs, the parameter table on the devices
-(:func:`_table_on`) and the statistics."""
+``_call_trace_kernel`` is the ctypes call; ``_quantile_plan`` / ``_interpolate`` are the quantiles of a select's result. Here
+remain the kernels' outputs (``_hip_*``), the one way to call them or their injected models (:func:`_run`, with the parameter
+table on the devices: :func:`_table_on`), the chunked write-then-select of ``predict`` and ``predict_response``
+(:func:`_select_by_obs_blocks`) and the statistics."""
 import ctypes
 import weakref
 
@@ -69,12 +72,17 @@ def _members(target):
                     "(the family that carries its data); got %r" % (target,))
 
 
+def _own_table(target, members):
+    """The target's own parameter rows, table[G, row_len] on the host."""
+    return np.ascontiguousarray(target.params, dtype=np.float64).reshape(len(members), -1)
+
+
 def _scored(target, members, data):
     """(table[G, row_len] (host), the GLMs whose y and constants apply) for the training data or for held-out ``data``."""
     from .targets import GLM, Batched
 
     if data is None:
-        return np.ascontiguousarray(target.params, dtype=np.float64).reshape(len(members), -1), members
+        return _own_table(target, members), members
     if isinstance(target, Batched):
         pairs = list(data)
         if len(pairs) != len(members) or any(not isinstance(p, (tuple, list)) or len(p) != 2 for p in pairs):
@@ -116,6 +124,25 @@ def _table_on(target, table, device, cache=None):
     return held[key]
 
 
+def _run(fn, hip, b, target, table, cache, *args):
+    """One kernel call on the block ``b`` of draws: the injected ``fn(b, table, *args)`` (tests of the host logic; ``table`` is
+    then the host table of parameter rows), or else the HIP call ``hip`` on the block as the kernel reads it, with the table on
+    the block's device (``cache``: as for :func:`_table_on`)."""
+    if fn is not None:
+        return fn(b, table, *args)
+    b = diagnostics._device_block(b)
+    return hip(b, _table_on(target, table, b.device, cache), *args)
+
+
+def _block_range(rng, n, refusal=None):
+    """(lo, hi) of the half-open, non-empty range ``rng`` of [0, n) (None: all of it), or ValueError: ``refusal``, by default
+    that of an ``obs_blocks=`` of n blocks of 64 observations."""
+    lo, hi = (0, n) if rng is None else (int(rng[0]), int(rng[1]))
+    if not (0 <= lo < hi <= n):
+        raise ValueError(refusal or "obs_blocks=%r of %d: a half-open, non-empty range" % (rng, n))
+    return lo, hi
+
+
 def pointwise_stats(x, target, data=None, chains_per_group=None, first_chain=0, stats_fn=None, group=None):
     """The six planes ``n, m, S, mean, M2, sum_mu`` of the pointwise log-likelihood, a dict of float64 tensors ``[G, N]`` on
     x's device (one group: a leading axis of 1).
@@ -140,10 +167,7 @@ def pointwise_stats(x, target, data=None, chains_per_group=None, first_chain=0, 
     cache = None if data is None else {}   # where the table of parameter rows lives on the devices
 
     def call(b, first):
-        if stats_fn is not None:
-            return stats_fn(b, table, first, job.per)[..., :n_obs]
-        b = diagnostics._device_block(b)
-        return _hip_pointwise(b, _table_on(target, table, b.device, cache), first, job.per)[..., :n_obs]
+        return _run(stats_fn, _hip_pointwise, b, target, table, cache, first, job.per)[..., :n_obs]
 
     tot = diagnostics._fan_out(job, job.g0, job.g0 + job.groups, call, merge)
     out = {name: tot[:, i] for i, name in enumerate(PLANES)}
@@ -194,7 +218,7 @@ def waic(x, target, data=None, **kw):
     return out
 
 
-# ---- PSIS-LOO (csrc/lmc_psis.hip; include/lmc_hip.h states the row algorithm) ---------------------------------------------
+# ---- PSIS-LOO (csrc/lmc_psis.hip: the rows; csrc/lmc_predict.hip: the array; include/lmc_hip.h states the row algorithm) -------
 def tail_len(S, reff=1.0):
     """M of a row of S draws at relative efficiency ``reff``: ``min(S // 5, ceil(3 sqrt(S / reff)))`` (Vehtari et al.)."""
     import math
@@ -233,12 +257,6 @@ def _hip_psis(l2, M):
     return out
 
 
-def _psis_block(l2, M, psis_fn):
-    if psis_fn is not None:
-        return psis_fn(l2, M)
-    return _hip_psis(l2, M)
-
-
 def psis(loglik, reff=1.0, psis_fn=None):
     """Pareto-smoothed importance sampling of every row of ``loglik[..., S]`` (a float64 ROCm tensor with a contiguous last
     axis: S log-likelihood values of one observation under S posterior draws) by the HIP kernel ``lmc_psis_rows``
@@ -275,7 +293,7 @@ def psis(loglik, reff=1.0, psis_fn=None):
             l2 = l2.contiguous()
     if l2.shape[0] == 0:
         raise ValueError("loglik holds no row")
-    out = _psis_block(l2, M, psis_fn)
+    out = (psis_fn or _hip_psis)(l2, M)
     names = {"elpd_i": 0, "pareto_k": 1, "n_tail": 2, "sigma": 3, "ess_w": 4, "min_loglik": 6}
     return {k: out[:, i].reshape(lead) for k, i in names.items()}
 
@@ -290,13 +308,6 @@ def _hip_loglik(x, table, first_chain, per, ob0, ob1):
     return out
 
 
-def _loglik_block(b, target, table, first, per, ob0, ob1, loglik_fn):
-    if loglik_fn is not None:
-        return loglik_fn(b, table, first, per, ob0, ob1)
-    b = diagnostics._device_block(b)
-    return _hip_loglik(b, _table_on(target, table, b.device), first, per, ob0, ob1)
-
-
 def pointwise_loglik(x, target, groups=None, obs_blocks=None, loglik_fn=None):
     """The pointwise log-likelihood array itself, ``[G', 64 * blocks, S]`` on the device: ``out[g, i, s]`` is ``l`` of
     observation ``64 * ob0 + i`` of group ``g`` under draw ``s = (chain within the group) * draws + t`` -- the bits that
@@ -306,17 +317,16 @@ def pointwise_loglik(x, target, groups=None, obs_blocks=None, loglik_fn=None):
     list of per-GPU blocks every group must lie in one block, and the result is gathered on the first block's device."""
     members = _members(target)
     job = diagnostics._trace_job(x, None, 0, target, whole_job=True, whole_groups=True)   # a posterior's draws form one row
-    table, per = np.ascontiguousarray(target.params, dtype=np.float64).reshape(len(members), -1), job.per
+    table, per = _own_table(target, members), job.per
     nob = (members[0].n_obs + 63) // 64
-    g_lo, g_hi = (0, len(members)) if groups is None else (int(groups[0]), int(groups[1]))
-    ob0, ob1 = (0, nob) if obs_blocks is None else (int(obs_blocks[0]), int(obs_blocks[1]))
-    if not (0 <= g_lo < g_hi <= len(members)) or not (0 <= ob0 < ob1 <= nob):
-        raise ValueError("groups=%r of %d, obs_blocks=%r of %d: half-open, non-empty ranges" % (groups, len(members), obs_blocks, nob))
+    refusal = "groups=%r of %d, obs_blocks=%r of %d: half-open, non-empty ranges" % (groups, len(members), obs_blocks, nob)
+    g_lo, g_hi = _block_range(groups, len(members), refusal)
+    ob0, ob1 = _block_range(obs_blocks, nob, refusal)
     parts = []
     for b, f in zip(job.held, job.firsts):   # (a gather of whole groups, not a fan-out: nothing is combined)
         lo, hi = max(g_lo, f // per), min(g_hi, (f + int(b.shape[0])) // per)
         if lo < hi:
-            parts.append(_loglik_block(b[lo * per - f:hi * per - f], target, table, lo * per, per, ob0, ob1, loglik_fn))
+            parts.append(_run(loglik_fn, _hip_loglik, b[lo * per - f:hi * per - f], target, table, None, lo * per, per, ob0, ob1))
     return parts[0] if len(parts) == 1 else torch.cat([p.to(parts[0].device) for p in parts], dim=0)
 
 
@@ -340,7 +350,7 @@ def loo(x, target, reff=1.0, scratch_bytes=1 << 30, psis_fn=None, loglik_fn=None
                          "held-out points)")
     members = _members(target)
     job = diagnostics._trace_job(x, None, 0, target, whole_job=True, whole_groups=True)   # a posterior's draws form one row
-    table, per = np.ascontiguousarray(target.params, dtype=np.float64).reshape(len(members), -1), job.per
+    table, per = _own_table(target, members), job.per
     S = per * job.n_draws
     M = _checked_tail_len(S, reff)
     n_obs = members[0].n_obs
@@ -360,8 +370,8 @@ def loo(x, target, reff=1.0, scratch_bytes=1 << 30, psis_fn=None, loglik_fn=None
         else:
             chunks = [(g, g + 1, ob, min(ob + cap, nob)) for g in range(n_g) for ob in range(0, nob, cap)]
         for lo, hi, ob0, ob1 in chunks:
-            ll = _loglik_block(b[lo * per:hi * per], target, table, f + lo * per, per, ob0, ob1, loglik_fn)
-            res = _psis_block(ll.reshape(-1, S), M, psis_fn).reshape(hi - lo, (ob1 - ob0) * 64, len(PSIS_COLUMNS))
+            ll = _run(loglik_fn, _hip_loglik, b[lo * per:hi * per], target, table, None, f + lo * per, per, ob0, ob1)
+            res = (psis_fn or _hip_psis)(ll.reshape(-1, S), M).reshape(hi - lo, (ob1 - ob0) * 64, len(PSIS_COLUMNS))
             rows[g_b + lo:g_b + hi, ob0 * 64:ob1 * 64] = res.to(dev)
             del ll
     rows = rows[:, :n_obs]
@@ -398,7 +408,7 @@ def _predicted(target, members, X_new):
     from .targets import GLM, Batched
 
     if X_new is None:
-        return np.ascontiguousarray(target.params, dtype=np.float64).reshape(len(members), -1), members[0].n_obs
+        return _own_table(target, members), members[0].n_obs
     if isinstance(target, Batched):
         designs = list(X_new)
         if len(designs) != len(members):
@@ -433,14 +443,6 @@ def _hip_linpred(x, table, first_chain, per, ob0, ob1, want_eta=True, want_stats
     return eta, stats
 
 
-def _linpred_block(b, target, table, cache, first, per, ob0, ob1, linpred_fn, want_eta=True, want_stats=True):
-    """``cache``: as for :func:`_table_on` -- None where the table is the target's own, a dict of this call for ``X_new``."""
-    if linpred_fn is not None:
-        return linpred_fn(b, table, first, per, ob0, ob1, want_eta, want_stats)
-    b = diagnostics._device_block(b)
-    return _hip_linpred(b, _table_on(target, table, b.device, cache), first, per, ob0, ob1, want_eta, want_stats)
-
-
 def linear_predictor(x, target, X_new=None, obs_blocks=None, linpred_fn=None):
     """The linear predictor itself and its moments, from ONE tensor of draws ``x[chains, draws, d]`` (the whole job of
     ``target``) -> ``(eta[chains, draws, W], stats)``: ``eta[c, t, i]`` is ``X_new[64 * ob0 + i] @ x[c, t]`` on the row of
@@ -454,12 +456,37 @@ def linear_predictor(x, target, X_new=None, obs_blocks=None, linpred_fn=None):
     members = _members(target)
     job = diagnostics._trace_job(x, None, 0, target, whole_job=True)
     table, n_new = _predicted(target, members, X_new)
-    nob = (n_new + 63) // 64
-    ob0, ob1 = (0, nob) if obs_blocks is None else (int(obs_blocks[0]), int(obs_blocks[1]))
-    if not (0 <= ob0 < ob1 <= nob):
-        raise ValueError("obs_blocks=%r of %d: a half-open, non-empty range" % (obs_blocks, nob))
-    eta, st = _linpred_block(job.held[0], target, table, None if X_new is None else {}, 0, job.per, ob0, ob1, linpred_fn)
+    ob0, ob1 = _block_range(obs_blocks, (n_new + 63) // 64)
+    eta, st = _run(linpred_fn, _hip_linpred, job.held[0], target, table, None if X_new is None else {}, 0, job.per, ob0, ob1,
+                   True, True)
     return eta, {name: st[:, i] for i, name in enumerate(MOMENT_PLANES)}
+
+
+def _select_by_obs_blocks(job, n_new, ranks, scratch_bytes, what, write, count_fn):
+    """Write an array ``[chains, draws, 64 k]`` of ``what`` by blocks of 64 of the ``n_new`` observations, then select from it:
+    yields ``diagnostics.order_statistics`` at ``ranks`` of every chunk, ``[G, len(ranks), 64 k]``, the chunks in order.
+    ``write(ob0, ob1)`` returns the written arrays of the job's blocks, each on its device. A chunk holds as many observation
+    blocks as fit into ``scratch_bytes`` with the select's counts of them -- ``chains x draws x 64 x 8`` bytes an observation
+    block over all devices, and 256 buckets x 64 columns x 8 bytes a rank and group -- and the select gets the rest through its
+    own ``scratch_bytes=``; ValueError if one observation block does not fit. Columns are independent, so the chunking does not
+    change a bit."""
+    from . import _abi
+
+    unit = job.chains * job.n_draws * 64 * 8
+    count_unit = 256 * 64 * 8 * min(len(set(ranks)), _abi.SELECT_MAX_RANKS)
+    nob = (n_new + 63) // 64
+    step = min(int(scratch_bytes) // (unit + count_unit), nob)
+    if step < 1:
+        raise ValueError("scratch_bytes=%d is below one block of 64 observations of %s, %d chains x %d draws x 64 x 8 = %d bytes, "
+                         "plus %d bytes of the select's counts of it" % (int(scratch_bytes), what, job.chains, job.n_draws, unit,
+                                                                        count_unit))
+    for ob0 in range(0, nob, step):
+        ob1 = min(ob0 + step, nob)
+        written = write(ob0, ob1)
+        os_ = diagnostics.order_statistics(written if len(written) > 1 else written[0], ranks, chains_per_group=job.per,
+                                           scratch_bytes=int(scratch_bytes) - (ob1 - ob0) * unit, count_fn=count_fn)
+        del written
+        yield os_
 
 
 def _inverse_link(likelihood, eta):
@@ -495,59 +522,34 @@ def predict(x, target, X_new=None, probs=(0.05, 0.5, 0.95), chains_per_group=Non
     chunking does not change a bit. ``linpred_fn`` (see :func:`linear_predictor`) and ``count_fn`` (see
     ``diagnostics.order_statistics``) replace the two HIP calls (tests of this logic); without ``linpred_fn`` a CPU tensor
     raises HipLibraryError. Not with an active process group."""
-    import math
-
-    from . import _abi
-
     members = _members(target)
     job = diagnostics._trace_job(x, chains_per_group, 0, target, whole_job=True)   # a group may straddle blocks
-    per, n_draws, dev = job.per, job.n_draws, job.device
-    probs =[float(p) for p in (probs.tolist() if hasattr(probs, "tolist") else probs)]
-    if not probs or any(not (0.0 <= p <= 1.0) for p in probs):
-        raise ValueError("probs must be a non-empty sequence of numbers in [0, 1] (got %r)" % (probs,))
+    per, dev, S = job.per, job.device, job.per * job.n_draws
+    probs, ranks, frac = diagnostics._quantile_plan(S, probs)
     table, n_new = _predicted(target, members, X_new)
-    G, Q, S = len(members), len(probs), per * n_draws
-    chains = per * G
-    # the interpolation of diagnostics.quantiles: h = p (S - 1), lo = floor(h), v[lo] + (v[min(lo + 1, S - 1)] - v[lo]) (h - lo)
-    h = [p * (S - 1) for p in probs]
-    lo = [int(math.floor(v)) for v in h]
-    hi = [min(k + 1, S - 1) for k in lo]
-    ranks = [0, S - 1] + lo + hi
-    # scratch: an observation block of eta, and one group's select counts of it (256 buckets x 64 columns x 8 bytes a rank)
-    unit = chains * n_draws * 64 * 8
-    count_unit = 256 * 64 * 8 * min(len(set(ranks)), _abi.SELECT_MAX_RANKS)
-    nob = (n_new + 63) // 64
-    step = min(int(scratch_bytes) // (unit + count_unit), nob)
-    if step < 1:
-        raise ValueError("scratch_bytes=%d is below one block of 64 observations of the linear predictor, %d chains x %d draws "
-                         "x 64 x 8 = %d bytes, plus %d bytes of the select's counts of it" % (int(scratch_bytes), chains, n_draws,
-                                                                                              unit, count_unit))
-    frac =torch.tensor([a - b for a, b in zip(h, lo)], dtype=torch.float64, device=dev).reshape(Q, 1)
+    G = len(members)
     liks = [m.likelihood for m in members]
     cache = None if X_new is None else {}   # where the table of parameter rows lives on the devices
-    moments, eta_q, mu_q, etas = [], [], [], []
+    moments, eta_q, mu_q = [], [], []
 
-    def call(b, first):   # the eta of the block stays on its device for the select; its moments are the part to merge
-        eta, st = _linpred_block(b, target, table, cache, first, per, ob0, ob1, linpred_fn)
-        etas.append(eta)
-        return st
+    def write(ob0, ob1):   # the eta of a block stays on its device for the select; its moments are the part to merge
+        etas = []
 
-    for ob0 in range(0, nob, step):
-        ob1 = min(ob0 + step, nob)
-        W = 64 * (ob1 - ob0)
-        tot = diagnostics._fan_out(job, 0, G, call, merge_moments)
-        os_ = diagnostics.order_statistics(etas if len(etas) > 1 else etas[0], ranks, chains_per_group=per,
-                                           scratch_bytes=int(scratch_bytes) - (ob1 - ob0) * unit, count_fn=count_fn)
-        del etas[:]
-        vmin, vmax = os_[:, 0], os_[:, 1]
-        vlo, vhi = os_[:, 2:2 + Q], os_[:, 2 + Q:]
-        bad = (torch.isnan(vmin) | torch.isnan(vmax)).unsqueeze(1)      # a NaN draw: every quantile NaN, as numpy's are
-        nan = torch.full((G, Q, W), float("nan"), dtype=torch.float64, device=dev)
-        eta_q.append(torch.where(bad, nan, vlo + (vhi - vlo) * frac))
-        mlo = torch.stack([_inverse_link(liks[g], vlo[g]) for g in range(G)])
-        mhi = torch.stack([_inverse_link(liks[g], vhi[g]) for g in range(G)])
-        mu_q.append(torch.where(bad, nan, mlo + (mhi - mlo) * frac))
-        moments.append(tot)
+        def call(b, first):
+            eta, st = _run(linpred_fn, _hip_linpred, b, target, table, cache, first, per, ob0, ob1, True, True)
+            etas.append(eta)
+            return st
+
+        moments.append(diagnostics._fan_out(job, 0, G, call, merge_moments))
+        return etas
+
+    def mu_of(v):   # the member's inverse link, group by group
+        return torch.stack([_inverse_link(liks[g], v[g]) for g in range(G)])
+
+    for os_ in _select_by_obs_blocks(job, n_new, ranks, scratch_bytes, "the linear predictor", write, count_fn):
+        _vmin, _vmax, q, q_mu = diagnostics._interpolate(os_, frac, link=mu_of)
+        eta_q.append(q)
+        mu_q.append(q_mu)
     tot = torch.cat(moments, dim=-1)[..., :n_new]
     n = tot[:, 0]
     eta_mean, mu_mean = tot[:, 1], tot[:, 3]
@@ -581,13 +583,6 @@ def _hip_yrep(x, table, first_chain, per, ob0, ob1, seed):
     return y
 
 
-def _yrep_block(b, target, table, cache, first, per, ob0, ob1, seed, yrep_fn):
-    if yrep_fn is not None:
-        return yrep_fn(b, table, first, per, ob0, ob1, seed)
-    b = diagnostics._device_block(b)
-    return _hip_yrep(b, _table_on(target, table, b.device, cache), first, per, ob0, ob1, seed)
-
-
 def replicate(x, target, X_new=None, obs_blocks=None, random_seed=0, yrep_fn=None):
     """Replicated responses ``y_rep ~ p(y | q_s)`` of every draw, from ONE tensor of draws ``x[chains, draws, d]`` (the whole
     job of ``target``) -> ``y[chains, draws, W]`` on the device: ``y[c, t, i]`` is a bernoulli / poisson / gaussian response at
@@ -602,19 +597,9 @@ def replicate(x, target, X_new=None, obs_blocks=None, random_seed=0, yrep_fn=Non
     members = _members(target)
     job = diagnostics._trace_job(x, None, 0, target, whole_job=True)
     table, n_new = _predicted(target, members, X_new)
-    nob = (n_new + 63) // 64
-    ob0, ob1 = (0, nob) if obs_blocks is None else (int(obs_blocks[0]), int(obs_blocks[1]))
-    if not (0 <= ob0 < ob1 <= nob):
-        raise ValueError("obs_blocks=%r of %d: a half-open, non-empty range" % (obs_blocks, nob))
-    return _yrep_block(job.held[0], target, table, None if X_new is None else {}, 0, job.per, ob0, ob1, _seed32(random_seed),
-                       yrep_fn)
-
-
-def _probs(probs):
-    probs = [float(p) for p in (probs.tolist() if hasattr(probs, "tolist") else probs)]
-    if not probs or any(not (0.0 <= p <= 1.0) for p in probs):
-        raise ValueError("probs must be a non-empty sequence of numbers in [0, 1] (got %r)" % (probs,))
-    return probs
+    ob0, ob1 = _block_range(obs_blocks, (n_new + 63) // 64)
+    return _run(yrep_fn, _hip_yrep, job.held[0], target, table, None if X_new is None else {}, 0, job.per, ob0, ob1,
+                _seed32(random_seed))
 
 
 def predict_response(x, target, X_new=None, probs=(0.05, 0.5, 0.95), chains_per_group=None, scratch_bytes=1 << 30,
@@ -630,58 +615,35 @@ def predict_response(x, target, X_new=None, probs=(0.05, 0.5, 0.95), chains_per_
     NaN quantiles, as numpy's are. The result is a pure function of ``random_seed`` and the draws: ``scratch_bytes`` (the
     chunking over blocks of 64 observations, as in :func:`predict`), the list of per-GPU blocks and the devices do not change
     a bit. ``yrep_fn`` (see :func:`replicate`) and ``count_fn`` (``diagnostics.order_statistics``) replace the two HIP calls."""
-    import math
-
-    from . import _abi
-
     members = _members(target)
     job = diagnostics._trace_job(x, chains_per_group, 0, target, whole_job=True)   # a group may straddle blocks
-    per, n_draws, dev = job.per, job.n_draws, job.device
-    probs = _probs(probs)
+    per, S = job.per, job.per * job.n_draws
+    probs, ranks, frac = diagnostics._quantile_plan(S, probs)
     table, n_new = _predicted(target, members, X_new)
-    G, Q, S = len(members), len(probs), per * n_draws
-    chains = per * G
-    h = [p * (S - 1) for p in probs]
-    lo = [int(math.floor(v)) for v in h]
-    hi = [min(k + 1, S - 1) for k in lo]
-    ranks = [0, S - 1] + lo + hi
-    unit = chains * n_draws * 64 * 8
-    count_unit = 256 * 64 * 8 * min(len(set(ranks)), _abi.SELECT_MAX_RANKS)
-    nob = (n_new + 63) // 64
-    step = min(int(scratch_bytes) // (unit + count_unit), nob)
-    if step < 1:
-        raise ValueError("scratch_bytes=%d is below one block of 64 observations of the replicated responses, %d chains x %d "
-                         "draws x 64 x 8 = %d bytes, plus %d bytes of the select's counts of it" % (int(scratch_bytes), chains,
-                                                                                                    n_draws, unit, count_unit))
-    frac = torch.tensor([a - b for a, b in zip(h, lo)], dtype=torch.float64, device=dev).reshape(Q, 1)
     cache = None if X_new is None else {}
     seed = _seed32(random_seed)
     y_q, y_min, y_max = [], [], []
-    for ob0 in range(0, nob, step):
-        ob1 = min(ob0 + step, nob)
-        W = 64 * (ob1 - ob0)
-        ys = [_yrep_block(b, target, table, cache, f, per, ob0, ob1, seed, yrep_fn) for b, f in zip(job.held, job.firsts)]
-        os_ = diagnostics.order_statistics(ys if len(ys) > 1 else ys[0], ranks, chains_per_group=per,
-                                           scratch_bytes=int(scratch_bytes) - (ob1 - ob0) * unit, count_fn=count_fn)
-        del ys
-        vmin, vmax = os_[:, 0], os_[:, 1]
-        vlo, vhi = os_[:, 2:2 + Q], os_[:, 2 + Q:]
-        bad = (torch.isnan(vmin) | torch.isnan(vmax)).unsqueeze(1)
-        nan = torch.full((G, Q, W), float("nan"), dtype=torch.float64, device=dev)
-        y_q.append(torch.where(bad, nan, vlo + (vhi - vlo) * frac))
+
+    def write(ob0, ob1):
+        return [_run(yrep_fn, _hip_yrep, b, target, table, cache, f, per, ob0, ob1, seed) for b, f in zip(job.held, job.firsts)]
+
+    for os_ in _select_by_obs_blocks(job, n_new, ranks, scratch_bytes, "the replicated responses", write, count_fn):
+        vmin, vmax, q = diagnostics._interpolate(os_, frac)
         y_min.append(vmin)
         y_max.append(vmax)
+        y_q.append(q)
     return dict(y_quantiles=torch.cat(y_q, dim=-1)[..., :n_new], y_min=torch.cat(y_min, dim=-1)[..., :n_new],
                 y_max=torch.cat(y_max, dim=-1)[..., :n_new], n=S, probs=probs)
 
 
 def _hip_yrep_stats(x, table, first_chain, per, seed, centre):
-    """One call of lmc_glm_yrep_stats: x[chains, draws, d] (a ROCm tensor), table[n_rows, row_len] and centre[n_rows] on the
-    same device -> T[chains, draws, 7]."""
+    """One call of lmc_glm_yrep_stats: x[chains, draws, d] (a ROCm tensor), table[n_rows, row_len] on the same device and
+    centre[n_rows] (a host array; it goes there) -> T[chains, draws, 7]."""
     from . import _abi
 
     c, n, _d = x.shape
     n_rows, row_len = table.shape
+    centre = torch.from_numpy(centre).to(x.device)
     T = torch.empty((c, n, _abi.YREP_STATS), dtype=torch.float64, device=x.device)
     diagnostics._call_trace_kernel("lmc_glm_yrep_stats", x, table, row_len, n_rows, int(first_chain), int(per), int(seed), centre, T)
     return T
@@ -736,9 +698,9 @@ def ppc(x, target, random_seed=0, probs=(0.05, 0.5, 0.95), chains_per_group=None
     members = _members(target)
     job = diagnostics._trace_job(x, chains_per_group, 0, target, whole_job=True)   # a group may straddle blocks
     per, dev, S = job.per, job.device, job.per * job.n_draws
-    probs = _probs(probs)
+    probs = diagnostics._probs(probs)
     G, n_obs = len(members), members[0].n_obs
-    table = np.ascontiguousarray(target.params, dtype=np.float64).reshape(G, -1)
+    table = _own_table(target, members)
     seed = _seed32(random_seed)
     centre = np.array([float(m.y.sum()) / n_obs for m in members], dtype=np.float64)
     planes_obs = np.array([[m.y.sum(), ((m.y - c) ** 2).sum(), m.y.min(), m.y.max(), float((m.y == 0.0).sum())]
@@ -747,11 +709,7 @@ def ppc(x, target, random_seed=0, probs=(0.05, 0.5, 0.95), chains_per_group=None
     scaled = []
 
     def call(b, first):   # the five scales stay on the block's device; what is merged are sums and counts per group
-        if stats_fn is not None:
-            T = stats_fn(b, table, first, per, seed, centre)
-        else:
-            b = diagnostics._device_block(b)
-            T = _hip_yrep_stats(b, _table_on(target, table, b.device), first, per, seed, torch.from_numpy(centre).to(b.device))
+        T = _run(stats_fn, _hip_yrep_stats, b, target, table, None, first, per, seed, centre)
         g = (first + torch.arange(int(b.shape[0]), device=T.device)) // per
         tr = ppc_scales(T, n_obs, torch.from_numpy(centre).to(T.device)[g].unsqueeze(1))
         scaled.append(tr)

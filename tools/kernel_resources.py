@@ -6,7 +6,8 @@ import sys
 
 args = sys.argv[1:]
 unit = "lmc_engine"
-if args and args[0] in ("lmc_engine", "lmc_dense", "lmc_dense_coop", "lmc_wide", "lmc_diag", "lmc_yrep"):   # translation unit to analyse (default: the diagonal kernels)
+if args and args[0] in ("lmc_engine", "lmc_dense", "lmc_dense_coop", "lmc_wide", "lmc_diag", "lmc_yrep", "lmc_predict", "lmc_linpred",
+                        "lmc_psis"):   # translation unit to analyse (default: the diagonal kernels)
     unit = args.pop(0)
 cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-c", "-mllvm", "-disable-machine-licm",
        "-I", "littlemcmc_amd/csrc", "-Rpass-analysis=kernel-resource-usage", "-o", "/tmp/lmc_kres.o",
