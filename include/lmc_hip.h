@@ -881,6 +881,29 @@ int lmc_glm_yrep_stats(const double* x, int64_t chains, int64_t draws_stride, in
                        const double* rows, int64_t row_len, int64_t n_rows, int64_t first_chain, int64_t chains_per_group,
                        uint32_t seed, const double* centre, double* T, void* stream);
 
+/* ---- threshold counts of the draws in HBM: which rank a value has (additive within ABI 9; littlemcmc_amd/diagnostics.py:
+ * threshold_counts, prob, direction, rope; predictive.exceedance; sbc.sbc_glm; csrc/lmc_threshold.hip) ----------------------
+ * x, chains, draws_stride, dim, t0, n, first_chain, chains_per_group: the trace block, sub-series and groups of
+ * lmc_select_digit_counts -- the block touches groups g0 .. g1, and a first or last group that lies only partly inside the
+ * block is counted over its chains that are present. thresholds is [g1 - g0 + 1][n_thresholds][dim] doubles (DEVICE) and
+ * counts is [g1 - g0 + 1][2 n_thresholds + 1][dim] (DEVICE, overwritten). With K = n_thresholds, c = thresholds[g][k][j] and
+ * the draws v of dimension j, rows [t0, t0 + n), chains of group g0 + g present in the block:
+ *   counts[g][2 k][j]     = the number of draws with v < c
+ *   counts[g][2 k + 1][j] = the number of draws with v == c
+ *   counts[g][2 K][j]     = the number of draws with v != v (NaN)
+ * The comparisons are IEEE NUMERIC comparisons, not the select's total order on the bits: -0.0 == +0.0; a NaN draw is neither
+ * below nor equal to anything; a NaN threshold counts 0 and 0; +-inf thresholds and draws compare as numbers. The number of
+ * draws above c is the group's draws minus below, equal and NaN. The counts are integers and add over chains, blocks and
+ * GPUs exactly. The trace is read once whatever K is. The work is enqueued on `stream` of the current device (a memset of
+ * counts, then one kernel); integer atomics only, so the result does not depend on the order of arrival.
+ * Refused with LMC_ERR_INVALID before any HIP call: NULL x, thresholds or counts; n_thresholds outside 1 ..
+ * LMC_THRESHOLD_MAX; n at or beyond 2^31 (a workgroup's 32-bit counters hold the draws of at least two chains); what
+ * lmc_select_digit_counts refuses of the trace view and the grouping; a result of 2^39 counters or more. */
+#define LMC_THRESHOLD_MAX 16
+int lmc_diag_threshold_counts(const double* x, int64_t chains, int64_t draws_stride, int32_t dim, int64_t t0, int64_t n,
+                              int64_t first_chain, int64_t chains_per_group, int32_t n_thresholds, const double* thresholds,
+                              int64_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

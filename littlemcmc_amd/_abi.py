@@ -23,6 +23,7 @@ GLM_MAX_DIM, GLM_HEADER, GLM_MAX_ROW = 512, 8, 1 << 29
 PSIS_MAX_TAIL = 4096   # include/lmc_hip.h: LMC_PSIS_MAX_TAIL, the sorted tail of a row lives in LDS (32 KiB of doubles)
 SELECT_MAX_RANKS = 16   # include/lmc_hip.h: LMC_SELECT_MAX_RANKS, the rank slots of one lmc_select_digit_counts call
 CROSS_MAX_DIM = 512   # include/lmc_hip.h: LMC_CROSS_MAX_DIM, the widest co-moment matrix of lmc_diag_cross_moments
+THRESHOLD_MAX = 16   # include/lmc_hip.h: LMC_THRESHOLD_MAX, the thresholds of one lmc_diag_threshold_counts call
 YREP_STATS = 7   # include/lmc_hip.h: LMC_YREP_STATS, the planes of one draw of lmc_glm_yrep_stats
 STATUS_BAD_INITIAL_ENERGY = 1
 SDOT_NATIVE, SDOT_OPENBLAS_SKYLAKEX, SDOT_OPENBLAS_HASWELL = 0, 1, 2
@@ -218,6 +219,8 @@ _SIGNATURES = {
                                C.c_int64, C.c_int64, C.c_int64, C.c_uint32, _P, _P]),
     "lmc_glm_yrep_stats": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int64,
                                      C.c_int64, C.c_int64, C.c_uint32, _P, _P, _P]),
+    "lmc_diag_threshold_counts": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                            C.c_int32, _P, _P, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -1,5 +1,5 @@
-// The host-side prologue of a pass over the trace, stated ONCE for the eight entry points that make one (lmc_diag.hip,
-// lmc_select.hip, the two of lmc_predict.hip, lmc_linpred.hip, lmc_cross.hip, and the two of lmc_yrep.hip). Host code only: pure argument checks that return
+// The host-side prologue of a pass over the trace, stated ONCE for the nine entry points that make one (lmc_diag.hip,
+// lmc_select.hip, the two of lmc_predict.hip, lmc_linpred.hip, lmc_cross.hip, the two of lmc_yrep.hip, and lmc_threshold.hip). Host code only: pure argument checks that return
 // LMC_ERR_INVALID before any HIP call, and the one host look at the headers of a GLM table. What differs per pass -- its
 // output pointers, its own limits, its launch geometry -- stays in the entry point.
 #pragma once

@@ -27,7 +27,12 @@ histograms of key digits from ``lmc_select_digit_counts`` (csrc/lmc_select.hip),
 
 Posterior covariance and correlation per posterior (``cross_moments``, ``covariance``, ``contrasts``, after them) are one
 contraction over the (chain, draw) rows of every group on the FP64 matrix cores, ``lmc_diag_cross_moments``
-(csrc/lmc_cross.hip); blocks merge by Chan's rule for matrices (``merge_cross_moments``)."""
+(csrc/lmc_cross.hip); blocks merge by Chan's rule for matrices (``merge_cross_moments``).
+
+Posterior probabilities (``threshold_counts``, ``prob``, ``direction``, ``rope``, after ``tail_ess``) are the inverse question
+of the select, which rank a value has: per (posterior, coefficient, threshold) the draws below and equal to the threshold
+from ``lmc_diag_threshold_counts`` (csrc/lmc_threshold.hip), one read of the trace for up to 16 thresholds, integers that add
+over chains and GPUs. ``sbc`` takes the ranks of simulation-based calibration from it."""
 import collections
 import ctypes
 import math
@@ -764,29 +769,186 @@ def tail_ess(x, probs=(0.05, 0.95), split=True, chains_per_group=None, chunk_dim
     ``**kw`` goes to ``order_statistics``; ``stats_fn`` to ``sufficient_stats``."""
     q = quantiles(x, probs, chains_per_group=chains_per_group, **kw)["quantiles"]
     job = _select_job(x, chains_per_group)
-    held, firsts, per, G, d = job.held, job.firsts, job.per, job.groups, job.d
     best = None
     for k in range(q.shape[-2]):
-        parts = []
-        for lo in range(0, d, int(chunk_dims)):
-            hi = min(lo + int(chunk_dims), d)
-            ind = []
-            for b, f in zip(held, firsts):
-                qk = q[..., k, lo:hi].to(b.device)
-                if chains_per_group is not None:   # the quantile of every chain's own group
-                    rows = (torch.arange(int(b.shape[0]), device=b.device) + f) // per
-                    qk = qk.index_select(0, rows)
-                    ind.append((b[:, :, lo:hi] <= qk.unsqueeze(1)).to(torch.float64))
-                else:
-                    ind.append((b[:, :, lo:hi] <= qk).to(torch.float64))
-            st = sufficient_stats(ind if len(ind) > 1 else ind[0], split=split, stats_fn=stats_fn, chains_per_group=chains_per_group)
-            parts.append(finalize(st)["ess"].to(q.device))
-        ess = torch.cat(parts, dim=-1)
+        ess = _indicator_ess(job, q[..., k, :], torch.le, split, chunk_dims, stats_fn, chains_per_group)
         best = ess if best is None else torch.minimum(best, ess)
     out = {"ess_tail": best, "probs": [float(p) for p in probs]}
     if chains_per_group is not None:
-        out.update(groups=G, ess_tail_min=best.min(dim=-1).values)
+        out.update(groups=job.groups, ess_tail_min=best.min(dim=-1).values)
     return out
+
+
+def _indicator_ess(job, q, below, split, chunk_dims, stats_fn, chains_per_group):
+    """The (split) ESS of the indicator ``below(x, q)`` of the job's draws -> [d] on q's device, [G, d] with ``chains_per_group``
+    (q is then [G, d]: every chain is compared with the value of its own group). ``below`` is ``torch.le`` (tail_ess) or
+    ``torch.lt`` (prob). The indicator is built for ``chunk_dims`` dimensions at a time -- the temporary is chains x draws x
+    chunk_dims doubles -- and goes through ``sufficient_stats`` / ``finalize`` like any draws."""
+    parts = []
+    for lo in range(0, job.d, int(chunk_dims)):
+        hi = min(lo + int(chunk_dims), job.d)
+        ind = []
+        for b, f in zip(job.held, job.firsts):
+            qk = q[..., lo:hi].to(b.device)
+            if chains_per_group is not None:   # the value of every chain's own group
+                rows = (torch.arange(int(b.shape[0]), device=b.device) + f) // job.per
+                qk = qk.index_select(0, rows)
+                ind.append(below(b[:, :, lo:hi], qk.unsqueeze(1)).to(torch.float64))
+            else:
+                ind.append(below(b[:, :, lo:hi], qk).to(torch.float64))
+        st = sufficient_stats(ind if len(ind) > 1 else ind[0], split=split, stats_fn=stats_fn, chains_per_group=chains_per_group)
+        parts.append(finalize(st)["ess"].to(q.device))
+    return torch.cat(parts, dim=-1)
+
+
+# ---- threshold counts of the trace in place: P(q < c), probability of direction, ROPE, ranks for calibration --------------
+# The inverse question of the select: which rank a value has. Per (posterior, coefficient, threshold) the draws below and
+# equal to the threshold, and per (posterior, coefficient) the NaN draws (include/lmc_hip.h: lmc_diag_threshold_counts,
+# csrc/lmc_threshold.hip): integers that add over chains, chain blocks and GPUs exactly. IEEE numeric comparisons.
+def _hip_threshold_counts(x, first_chain, per, thresholds):
+    """One call of lmc_diag_threshold_counts over x[chains, draws, d] (a ROCm tensor): thresholds [groups touched, K, d] float64
+    on x's device, K <= 16 -> counts [groups touched, 2 K + 1, d] int64 there (2k: below, 2k + 1: equal, 2K: NaN draws)."""
+    x = _device_block(x)
+    c, _n, d = x.shape
+    touched = _touched(first_chain, c, per)[1]
+    thresholds = thresholds.contiguous()
+    K = int(thresholds.shape[1]) if thresholds.dim() == 3 else 0
+    if tuple(thresholds.shape) != (touched, K, d) or thresholds.dtype != torch.float64 or thresholds.device != x.device:
+        raise ValueError("thresholds must be float64 [%d, K, %d] on %s" % (touched, d, x.device))
+    out = torch.empty((touched, 2 * K + 1, d), dtype=torch.int64, device=x.device)
+    _call_trace_kernel("lmc_diag_threshold_counts", x, int(first_chain), int(per), K, thresholds, out)
+    return out
+
+
+def _threshold_block(thresholds, G, d, grouped):
+    """``thresholds`` as a float64 tensor [G, K, d]: [K, d]; a scalar, [d] or 1-D of length K (a length of d is a [d]), all
+    broadcast to [K, d] and shared by the groups; with ``grouped`` also [G, K, d]. ValueError for any other shape."""
+    t = torch.as_tensor(thresholds, dtype=torch.float64)
+    if t.dim() == 0:
+        t = t.reshape(1, 1)
+    elif t.dim() == 1:
+        t = t.reshape(1, d) if t.shape[0] == d else t.reshape(-1, 1)
+    if t.dim() == 2 and t.shape[0] >= 1 and t.shape[1] in (1, d):
+        return t.expand(t.shape[0], d).unsqueeze(0).expand(G, -1, -1)
+    if t.dim() == 3 and grouped and t.shape[0] == G and t.shape[1] >= 1 and t.shape[2] == d:
+        return t
+    raise ValueError("thresholds must be a scalar, [%d], [K] or [K, %d]%s (got shape %s)"
+                     % (d, d, ", or [%d, K, %d]" % (G, d) if grouped else "", tuple(t.shape)))
+
+
+def threshold_counts(x, thresholds, chains_per_group=None, count_fn=None):
+    """How many draws in HBM lie below and at each threshold -> dict(less[K, d], equal[K, d] int64, nan[d] int64, n = S): per
+    coefficient j and threshold k, over the S = chains of a group x draws values v of the coefficient, ``less`` counts v < c,
+    ``equal`` v == c and ``nan`` the NaN draws, so S - less - equal - nan lie above. With ``chains_per_group=per`` (one posterior
+    per ``per`` consecutive chains) less, equal [G, K, d] and nan [G, d]. The comparisons are IEEE numeric ones: -0.0 == +0.0, a
+    NaN draw is neither below nor equal to anything, a NaN threshold counts 0 and 0. ``less`` is the RANK of the threshold
+    among the draws: the inverse of ``order_statistics``.
+
+    x is one tensor [chains, draws, d], or the list of per-GPU blocks of one job (``trace_tensor(engine_group)``): every block
+    is counted on its own device at its running first chain, the integer counts are added on the first block's device, and a
+    group may straddle blocks. ``thresholds`` is array-like: [K, d]; a scalar, [d] or 1-D of length K, broadcast to [K, d] (a
+    1-D length of d is read as [d]); with ``chains_per_group`` also [G, K, d], each posterior its own. One pass over the trace
+    (lmc_diag_threshold_counts) serves up to 16 thresholds; more run in rounds of 16. ``count_fn(x, first_chain, per,
+    thresholds[groups touched, K, d]) -> counts[groups touched, 2 K + 1, d]`` replaces the HIP call (tests of this logic only);
+    without it a CPU tensor raises HipLibraryError. Not with an active process group."""
+    from . import _abi
+
+    job = _trace_job(x, chains_per_group, whole_job=True)
+    G, d, dev = job.groups, job.d, job.device
+    thr = _threshold_block(thresholds, G, d, chains_per_group is not None).to(dev)
+    K = int(thr.shape[1])
+    fn = _hip_threshold_counts if count_fn is None else count_fn
+
+    def call(b, first):
+        off, touched = _touched(first, int(b.shape[0]), job.per)
+        return fn(b, first, job.per, part[off:off + touched].to(b.device).contiguous())
+
+    less = torch.empty((G, K, d), dtype=torch.int64, device=dev)
+    equal = torch.empty((G, K, d), dtype=torch.int64, device=dev)
+    nan = None
+    for k0 in range(0, K, _abi.THRESHOLD_MAX):
+        k1 = min(k0 + _abi.THRESHOLD_MAX, K)
+        part = thr[:, k0:k1]
+        if len(job.held) == 1:   # one block holds all chains: its counts are the sum -- moved, not added to zeros
+            cnt = call(job.held[0], 0).to(dev)
+        else:
+            cnt = _fan_out(job, 0, G, call, torch.add)
+        less[:, k0:k1], equal[:, k0:k1], nan = cnt[:, 0:2 * (k1 - k0):2], cnt[:, 1:2 * (k1 - k0):2], cnt[:, 2 * (k1 - k0)]
+    out = {"less": less, "equal": equal, "nan": nan, "n": job.per * job.n_draws}
+    if chains_per_group is None:
+        out.update(less=less[0], equal=equal[0], nan=nan[0])
+    return out
+
+
+def _divisor(S, like):
+    """S as a tensor divisor next to ``like``: count / S is then ONE correctly rounded division on every device (a Python
+    scalar divisor may be turned into a multiplication by its reciprocal, which differs in the last bit)."""
+    return torch.tensor(float(S), dtype=torch.float64, device=like.device)
+
+
+def _nan_where(bad, t):
+    return torch.where(bad, torch.full_like(t, float("nan")), t)
+
+
+def prob(x, thresholds, chains_per_group=None, mcse=False, split=True, chunk_dims=8, stats_fn=None, **kw):
+    """Posterior probabilities from the trace in place -> dict(p_less, p_equal, p_greater [K, d] float64, n = S, n_nan[d]):
+    the counts of ``threshold_counts`` (``thresholds``, ``**kw`` go there) over S, and p_greater = (S - less - equal) / S;
+    [G, K, d] and n_nan[G, d] with ``chains_per_group``. P(q_e > 0) is ``prob(x, 0.0)["p_greater"]``. A (posterior,
+    coefficient) that holds a NaN draw is NaN at every threshold and no other is -- the rule ``quantiles`` keeps.
+
+    ``mcse=True`` adds ``ess`` and ``mcse = sqrt(p (1 - p) / ess)`` of p_less: ``ess`` is the (split) ESS of the indicator
+    x < c, built ``chunk_dims`` dimensions at a time as ``tail_ess`` builds its indicator (``stats_fn`` goes to
+    ``sufficient_stats``). An indicator that is constant (p_less of 0 or 1) has no autocorrelation to estimate: its ess and
+    mcse are NaN."""
+    tc = threshold_counts(x, thresholds, chains_per_group=chains_per_group, **kw)
+    bad = (tc["nan"] > 0).unsqueeze(-2)
+    less, equal = tc["less"].to(torch.float64), tc["equal"].to(torch.float64)
+    S = _divisor(tc["n"], less)
+    out = {"p_less": _nan_where(bad, less / S), "p_equal": _nan_where(bad, equal / S),
+           "p_greater": _nan_where(bad, (S - less - equal) / S), "n": tc["n"], "n_nan": tc["nan"]}
+    if mcse:
+        job = _trace_job(x, chains_per_group, whole_job=True)
+        thr = _threshold_block(thresholds, job.groups, job.d, chains_per_group is not None).to(job.device)
+        if chains_per_group is None:
+            thr = thr[0]
+        ess = torch.stack([_indicator_ess(job, thr[..., k, :], torch.lt, split, chunk_dims, stats_fn, chains_per_group)
+                           for k in range(thr.shape[-2])], dim=-2)
+        p = out["p_less"]
+        out.update(ess=ess, mcse=torch.sqrt(p * (1.0 - p) / ess))
+    return out
+
+
+def direction(x, chains_per_group=None, **kw):
+    """Probability of direction -> dict(pd[d], sign[d], n): ``pd = max(P(q > 0), P(q < 0))`` and ``sign`` = +1 where P(q > 0) >=
+    P(q < 0), else -1 (float64); [G, d] with ``chains_per_group``. One threshold, 0, of ``prob`` (``**kw`` goes there); NaN where
+    the coefficient holds a NaN draw."""
+    p = prob(x, 0.0, chains_per_group=chains_per_group, **kw)
+    pos, neg = p["p_greater"][..., 0, :], p["p_less"][..., 0, :]
+    sign = torch.where(pos >= neg, torch.ones_like(pos), -torch.ones_like(pos))
+    return {"pd": torch.maximum(pos, neg), "sign": _nan_where(torch.isnan(pos), sign), "n": p["n"]}
+
+
+def rope(x, low, high, chains_per_group=None, **kw):
+    """Region of practical equivalence -> dict(inside, below, above [d], n): ``inside = P(low <= q <= high)``, ``below = P(q <
+    low)``, ``above = P(q > high)``; [G, d] with ``chains_per_group``. ``low`` and ``high`` are scalars or [d] (with
+    ``chains_per_group`` also [G, d]), low <= high. The two thresholds go through ONE pass of ``threshold_counts`` (``**kw``
+    goes there): ``inside = (less_high + equal_high - less_low) / S``. NaN where the coefficient holds a NaN draw."""
+    job = _trace_job(x, chains_per_group, whole_job=True)
+    lead = (job.groups, job.d) if chains_per_group is not None else (job.d,)
+    try:
+        lo = torch.as_tensor(low, dtype=torch.float64).to(job.device).expand(lead)
+        hi = torch.as_tensor(high, dtype=torch.float64).to(job.device).expand(lead)
+    except RuntimeError:
+        raise ValueError("low and high must be scalars or broadcast to %s" % (lead,))
+    if bool((lo > hi).any()):
+        raise ValueError("rope needs low <= high")
+    tc = threshold_counts(x, torch.stack([lo, hi], dim=-2), chains_per_group=chains_per_group, **kw)
+    bad = tc["nan"] > 0
+    less, equal = tc["less"].to(torch.float64), tc["equal"].to(torch.float64)
+    S = _divisor(tc["n"], less)
+    less_lo, less_hi, equal_hi = less[..., 0, :], less[..., 1, :], equal[..., 1, :]
+    return {"inside": _nan_where(bad, (less_hi + equal_hi - less_lo) / S), "below": _nan_where(bad, less_lo / S),
+            "above": _nan_where(bad, (S - less_hi - equal_hi) / S), "n": tc["n"]}
 
 
 # ---- posterior covariance and correlation per posterior: the co-moment matrix of the draws in place ------------------------

@@ -14,7 +14,8 @@ restatement of the kernel's block through ``stats_fn`` (as ``diagnostics.summari
 Further down: PSIS-LOO (``psis``, ``loo``; csrc/lmc_psis.hip smooths the array that ``lmc_glm_pointwise_loglik`` of
 csrc/lmc_predict.hip writes) and posterior predictions at new X (``linear_predictor``, ``predict``; csrc/lmc_linpred.hip) and
 replicated responses (``replicate``, ``predict_response``, ``ppc``; csrc/lmc_yrep.hip),
-each with its own kernel and its own injected model in the CPU tests.
+each with its own kernel and its own injected model in the CPU tests; ``exceedance`` (P(prediction < t) at new points) counts
+the written linear predictor with ``diagnostics.threshold_counts`` (csrc/lmc_threshold.hip).
 
 What the passes over the trace share is stated once, in ``diagnostics``: ``_trace_job`` answers "what is x?" (one tensor or
 the per-GPU blocks of a job, chains per group, the groups touched) with every refusal, each pass naming the rule it wants in
@@ -562,6 +563,72 @@ def predict(x, target, X_new=None, probs=(0.05, 0.5, 0.95), chains_per_group=Non
     return dict(eta_mean=eta_mean, eta_sd=torch.sqrt(eta_var), mu_mean=mu_mean, mu_sd=torch.sqrt(mu_var),
                 eta_quantiles=torch.cat(eta_q, dim=-1)[..., :n_new], mu_quantiles=torch.cat(mu_q, dim=-1)[..., :n_new],
                 y_mean=y_mean, y_var=y_var, n=S, probs=probs)
+
+
+def _link(likelihood, t):
+    """The link of a threshold ``t`` on the mean response: logit | log | identity, monotone, so mu < t exactly where eta <
+    link(t) up to the rounding of the inverse link. A threshold at or beyond the end of mu's range maps to -inf / +inf (no
+    mu lies below 0; every bernoulli mu lies below 1 and beyond); NaN stays NaN."""
+    if likelihood == "gaussian":
+        return t
+    low = torch.full_like(t, float("-inf"))
+    if likelihood == "poisson":
+        return torch.where(t <= 0, low, torch.log(t.clamp(min=0.0)))
+    inner = t.clamp(min=0.0, max=1.0)
+    return torch.where(t <= 0, low, torch.where(t >= 1, -low, torch.log(inner) - torch.log1p(-inner)))
+
+
+def exceedance(x, target, X_new=None, thresholds=0.0, scale="eta", chains_per_group=None, scratch_bytes=1 << 30,
+               linpred_fn=None, count_fn=None):
+    """P(prediction < t) at new points, counted over the draws in HBM -> dict(p_less, p_equal, p_greater [G, K, N_new] float64,
+    n = S, n_nan [G, N_new]) for a ``GLM`` (G = 1) or every posterior of a ``Batched`` of GLMs; ``1 - p_less - p_equal`` is
+    ``p_greater``, e.g. P(p_new > 0.5) of a bernoulli fit is ``exceedance(x, tgt, X_new, thresholds=0.5, scale="mu")["p_greater"]``.
+    ``thresholds`` is what ``diagnostics.threshold_counts`` takes with N_new in place of d: a scalar, 1-D of length K, [K, N_new]
+    or [G, K, N_new]. ``scale="eta"`` compares the linear predictor; ``scale="mu"`` the mean response, whose thresholds are
+    mapped through the member's monotone link on the host (logit | log | identity) and compared on the eta scale -- the
+    definition ``predict`` uses for its mu quantiles. A (posterior, point) with a NaN prediction is NaN.
+
+    The linear predictor is written (``lmc_glm_linpred``, the kernel of ``predict``) in chunks of blocks of 64 observations that
+    stay within ``scratch_bytes`` -- ``chains x draws x 64 x 8`` bytes an observation block over all devices; ValueError if one
+    does not fit -- and each chunk, which is trace-shaped, is counted with ``threshold_counts``. Columns are independent, so the
+    chunking does not change a count. ``x`` is one tensor or the list of per-GPU blocks of the job. ``linpred_fn`` (see
+    :func:`linear_predictor`) and ``count_fn`` (see ``diagnostics.threshold_counts``) replace the two HIP calls."""
+    if scale not in ("eta", "mu"):
+        raise ValueError("scale must be 'eta' or 'mu' (got %r)" % (scale,))
+    members = _members(target)
+    job = diagnostics._trace_job(x, chains_per_group, 0, target, whole_job=True)
+    per, dev, G = job.per, job.device, len(members)
+    table, n_new = _predicted(target, members, X_new)
+    thr = diagnostics._threshold_block(thresholds, G, n_new, True)
+    if scale == "mu":
+        thr = torch.stack([_link(m.likelihood, thr[g]) for g, m in enumerate(members)])
+    K, nob = int(thr.shape[1]), (n_new + 63) // 64
+    padded = torch.full((G, K, 64 * nob), float("nan"), dtype=torch.float64)   # a padding column counts nothing
+    padded[..., :n_new] = thr
+    unit = job.chains * job.n_draws * 64 * 8
+    step = min(int(scratch_bytes) // unit, nob)
+    if step < 1:
+        raise ValueError("scratch_bytes=%d is below one block of 64 observations of the linear predictor, %d chains x %d draws x "
+                         "64 x 8 = %d bytes" % (int(scratch_bytes), job.chains, job.n_draws, unit))
+    cache = None if X_new is None else {}
+    less, equal, nan = [], [], []
+    for ob0 in range(0, nob, step):
+        ob1 = min(ob0 + step, nob)
+        etas = [_run(linpred_fn, _hip_linpred, b, target, table, cache, f, per, ob0, ob1, True, False)[0]
+                for b, f in zip(job.held, job.firsts)]
+        tc = diagnostics.threshold_counts(etas if len(etas) > 1 else etas[0], padded[..., 64 * ob0:64 * ob1],
+                                          chains_per_group=per, count_fn=count_fn)
+        del etas
+        less.append(tc["less"].to(dev))
+        equal.append(tc["equal"].to(dev))
+        nan.append(tc["nan"].to(dev))
+    less, equal = (torch.cat(v, dim=-1)[..., :n_new].to(torch.float64) for v in (less, equal))
+    n_nan = torch.cat(nan, dim=-1)[..., :n_new]
+    bad = (n_nan > 0).unsqueeze(-2)
+    S = diagnostics._divisor(job.per * job.n_draws, less)   # (a tensor divisor: a division)
+    nanned = lambda t: torch.where(bad, torch.full_like(t, float("nan")), t)   # noqa: E731
+    return {"p_less": nanned(less / S), "p_equal": nanned(equal / S), "p_greater": nanned((S - less - equal) / S),
+            "n": job.per * job.n_draws, "n_nan": n_nan}
 
 
 # ---- replicated responses (csrc/lmc_yrep.hpp, csrc/lmc_yrep.hip; include/lmc_hip.h: lmc_glm_yrep, lmc_glm_yrep_stats) --------

@@ -284,6 +284,35 @@ class GLM(DeviceTarget):
 
         return diagnostics.contrasts(self.covariance(x, **kw), L, ddof=kw.get("ddof", 1))
 
+    def prob(self, x, thresholds, **kw):
+        """``diagnostics.prob(x, thresholds, ...)``: ``p_less``, ``p_equal``, ``p_greater`` ``[K, d]`` of the coefficients against
+        the thresholds, counted over the draws ``x`` in HBM; ``prob(x, 0.0)["p_greater"]`` is P(q_e > 0)."""
+        from . import diagnostics
+
+        diagnostics._trace_job(x, None, 0, self, whole_job=True)
+        return diagnostics.prob(x, thresholds, **kw)
+
+    def direction(self, x, **kw):
+        """``diagnostics.direction(x, ...)``: the probability of direction ``pd[d]`` and its ``sign[d]``."""
+        from . import diagnostics
+
+        diagnostics._trace_job(x, None, 0, self, whole_job=True)
+        return diagnostics.direction(x, **kw)
+
+    def rope(self, x, low, high, **kw):
+        """``diagnostics.rope(x, low, high, ...)``: ``inside = P(low <= q <= high)``, ``below``, ``above`` ``[d]``."""
+        from . import diagnostics
+
+        diagnostics._trace_job(x, None, 0, self, whole_job=True)
+        return diagnostics.rope(x, low, high, **kw)
+
+    def exceedance(self, x, X_new=None, **kw):
+        """``predictive.exceedance(x, self, X_new, ...)``: P(prediction < t) at the points ``X_new`` (default: the training
+        design) -- ``p_less``, ``p_equal``, ``p_greater`` ``[1, K, N_new]`` on the scale ``"eta"`` or ``"mu"``."""
+        from . import predictive
+
+        return predictive.exceedance(x, self, X_new, **kw)
+
     def __repr__(self):
         return "GLM(%s, N=%d, d=%d)" % (self.likelihood, self.n_obs, self.d)
 
@@ -790,6 +819,32 @@ class Batched(DeviceTarget):
         from . import diagnostics
 
         return diagnostics.contrasts(self.covariance(x, **kw), L, ddof=kw.get("ddof", 1))
+
+    def prob(self, x, thresholds, **kw):
+        """``diagnostics.prob`` per posterior: ``p_less``, ``p_equal``, ``p_greater`` ``[G, K, d]`` against the thresholds ([K, d]
+        shared, or [G, K, d]), counted over the draws in HBM (one tensor or the list of per-GPU blocks)."""
+        from . import diagnostics
+
+        return diagnostics.prob(x, thresholds, chains_per_group=self._per(x), **kw)
+
+    def direction(self, x, **kw):
+        """``diagnostics.direction`` per posterior: the probability of direction ``pd[G, d]`` and its ``sign[G, d]``."""
+        from . import diagnostics
+
+        return diagnostics.direction(x, chains_per_group=self._per(x), **kw)
+
+    def rope(self, x, low, high, **kw):
+        """``diagnostics.rope`` per posterior: ``inside = P(low <= q <= high)``, ``below``, ``above`` ``[G, d]``."""
+        from . import diagnostics
+
+        return diagnostics.rope(x, low, high, chains_per_group=self._per(x), **kw)
+
+    def exceedance(self, x, X_new=None, **kw):
+        """``predictive.exceedance(x, self, X_new, ...)`` per posterior (GLM members): P(prediction < t) at ``X_new`` --
+        ``p_less``, ``p_equal``, ``p_greater`` ``[G, K, N_new]`` on the scale ``"eta"`` or ``"mu"``."""
+        from . import predictive
+
+        return predictive.exceedance(x, self, X_new, **kw)
 
     def pointwise_stats(self, x, **kw):
         """``predictive.pointwise_stats(x, self, ...)`` per posterior (GLM members): the per-observation statistics ``[G, N]``."""
